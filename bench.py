@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path: G1 MSM scalar-muls/s (+ Fr NTT elements/s, proofs/s) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up the 2^log_n-point SRS with its fixed-base tables and the scalars, runs
+W warm-up and K timed steps of the `value` leg below and prints the line.  --full adds every other leg and check listed below (the
+same MSM without tables, the closed-form check, pipelined, seams, NTT, other sizes, strong scaling, the N > 1 group legs, proofs,
+cpu_baseline).  --dump-outputs DIR writes what the last timed step handed its caller to DIR/msm_result.npy (see dump_outputs).
 
 N > 1 needs N ranks, one per GPU.  Launched by `python -m torch.distributed.run ... bench.py --gpus N ...` every process is a
 rank (RANK / LOCAL_RANK / WORLD_SIZE in the environment).  Launched bare (`python bench.py --gpus N`, WORLD_SIZE unset) the
@@ -59,6 +64,9 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="run every leg and check, not only the headline leg (the --skip-* / size options "
+                                                        "below shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write the last step's MSM result to DIR/msm_result.npy")
     ap.add_argument("--log-n", type=int, default=20, help="weak-scaling MSM points per GPU = 2^log_n")
     ap.add_argument("--ntt-log-n", type=int, default=20, help="NTT length per GPU = 2^ntt_log_n")
     ap.add_argument("--group-legs-child", default="", help=argparse.SUPPRESS)       # internal: JSON job of the child that runs the bp_init_multi legs
@@ -255,6 +263,14 @@ def cpu_baseline(sample_log_n, threads_all):
                                              "sample": "utils.rs:63-81 as written (n^2 terms, one pow each) at n = 2^8, %.2f s; cost grows as n^2" % (t6 - t5)}},
         "host": "%d logical CPUs" % (os.cpu_count() or 0),
     }
+
+
+def dump_outputs(out_dir, msm_result):
+    """--dump-outputs: the 96 bytes the last timed step returned (the G1 point of the MSM, uncompressed affine x || y, big-endian,
+    include/bp_msm_ntt.h) as a float64 array of the byte values 0..255 -- exact, so two builds compare byte for byte"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result.npy"), np.frombuffer(msm_result, dtype=np.uint8).astype(np.float64))
 
 
 def group_legs_child(job):
@@ -457,7 +473,7 @@ def main():
     ctx.comm_set_timeout_ms(args.comm_timeout_ms)
     exchange = bpd.ShardedMsm(ctx)                     # under nccl: joins the library's communicator (every step agreed on by all ranks), or raises on all
     # every leg's result; None / empty until the leg has run (the line is built from whatever is there)
-    pipelined = ntt = ntt_batch = ntt_cols = strong = group_commit = prove = None
+    other = weak_ok = pipelined = ntt = ntt_batch = ntt_cols = strong = group_commit = prove = None
     seams, sizes, red, legs_done, cols_all_box = {}, {}, {}, [], [None]
 
     def timed_msm(srs, d_scal, n, steps, warmup):
@@ -571,7 +587,8 @@ def main():
             print(json.dumps(build_line(per_rank, final)), flush=True)
 
     def build_line(per_rank, final):
-        elapsed, other_elapsed = red["elapsed"], red["other_elapsed"]
+        elapsed, other_elapsed = red["elapsed"], red.get("other_elapsed")
+        without_tables = not args.no_tables and other is not None          # the same MSM on raw points ran (--full)
         ntt_elapsed, prove_elapsed, prove_single = red.get("ntt_elapsed", 0.0), red.get("prove_elapsed", 0.0), red.get("prove_single", 0.0)
         strong_elapsed, cols_elapsed, cols_gather = red.get("strong_elapsed", 0.0), red.get("cols_elapsed", 0.0), red.get("cols_gather", 0.0)
         cols_all = cols_all_box[0]
@@ -595,7 +612,7 @@ def main():
                                       "build_s": table_build_s,
                                       "note": "the headline is a FIXED-BASE MSM: T[w][i] = 2^(window_bits w) P_i built once per SRS outside the "
                                               "timed region; value_without_tables is the same MSM on the raw points"},
-                       "value_without_tables": None if args.no_tables else units / other_elapsed,
+                       "value_without_tables": units / other_elapsed if without_tables else None,
                        "parallelism": "point-range x%d" % world, "ranks": world, "backend": args.backend if use_dist else None,
                        "msm_exchange": None if not use_dist else
                        ("bp_msm_g1_allgather: record -> ncclAllGather -> device pre-sum -> one D2H, all under the C ABI (capi_comm.hip); the only "
@@ -603,8 +620,8 @@ def main():
                         "waits bounded at %d ms" % (ctx.comm_stats()["collectives"], ctx.comm_stats()["timeout_ms"])
                         if exchange.c_path else "dist.ShardedMsm host-side gather (gloo rehearsal of the control flow)")},
             # the headline is a FIXED-BASE MSM (the SRS of a Setup with its window tables resident); the reference-shaped figures beside it:
-            "value_without_tables": None if args.no_tables else units / other_elapsed,
-            "ms_per_step_without_tables": None if args.no_tables else 1e3 * other_elapsed / args.steps,
+            "value_without_tables": units / other_elapsed if without_tables else None,
+            "ms_per_step_without_tables": 1e3 * other_elapsed / args.steps if without_tables else None,
             "first_commit_ms": None if args.no_tables else 1e3 * (table_build_s + elapsed / args.steps),
             "uncached_seam_ms_per_call": seams["msm_uncached_seam"]["ms_per_call"] if "msm_uncached_seam" in seams else None,
             "host_scalars_ms_per_step": seams["msm_host_scalars"]["ms_per_step"] if "msm_host_scalars" in seams else None,
@@ -620,10 +637,6 @@ def main():
             "register_only_rates_source": UBENCH["source"],
             "equals_closed_form": weak_ok,
             "exchange_ms": head["exchange_ms"],
-            ("msm_with_tables" if args.no_tables else "msm_without_tables"): {
-                "value": units / other_elapsed, "unit": "scalar-muls/s", "ms_per_step": 1e3 * other_elapsed / args.steps,
-                "device_ms": other["dev_ms"], "accumulate_ms": other["acc_ms"], "tail_ms": other["dev_ms"] - other["acc_ms"],
-                "window_bits": other["stats"]["window_bits"]},
             "ntt": None if not ntt else {"metric": "fr_ntt_elements_per_s", "value": world * nn * args.steps / ntt_elapsed, "unit": "elements/s",
                     "ms_per_step": 1e3 * ntt_elapsed / args.steps, "ms_per_blocking_call": ntt["blocking_ms"], "passes": ntt["passes"],
                     "kernel_le_step": ntt["kernel_le_step"], "spot_check": ntt_ok,
@@ -636,6 +649,11 @@ def main():
             # under a launcher a complete line goes out after every leg: which legs this one holds, and whether more will follow
             "legs_finished": list(legs_done), "provisional": not final,
         }
+        if other is not None:
+            line["msm_with_tables" if args.no_tables else "msm_without_tables"] = {
+                "value": units / other_elapsed, "unit": "scalar-muls/s", "ms_per_step": 1e3 * other_elapsed / args.steps,
+                "device_ms": other["dev_ms"], "accumulate_ms": other["acc_ms"], "tail_ms": other["dev_ms"] - other["acc_ms"],
+                "window_bits": other["stats"]["window_bits"]}
         if ntt_cols:
             line["ntt_columns"] = {
                 "metric": "fr_ntt_elements_per_s", "value": NTT_COLUMNS * nn * args.steps / cols_elapsed, "unit": "elements/s", "n_gpus": world,
@@ -695,7 +713,7 @@ def main():
                                          % args.prove_log_n,
                              "proof_sha_rank0": prove["sha"], "srs_and_circuit_setup_s": prove["setup_s"],
                              "synthetic_circuit_host_s": prove["circuit_host_s"]}
-        if final and world == 1 and not args.skip_cpu:
+        if final and world == 1 and args.full and not args.skip_cpu:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_log_n, min(64, os.cpu_count() or 1))
         return line
 
@@ -705,19 +723,34 @@ def main():
     scal = synthetic(n, 0x5EED0000 + args.log_n, rank * n)
     table_info, table_build_s = {"window_bits": 0, "windows": 0, "bytes": 0}, 0.0
     if args.no_tables:                  # secondary leg first: the other table setting, same inputs
-        t0 = time.perf_counter()
-        table_info = ctx.srs_precompute(srs, 0)
-        table_build_s = time.perf_counter() - t0
-        other = timed_msm(srs, scal, n, args.steps, args.warmup)
-        ctx.srs_precompute(srs, bp.SRS_TABLES_OFF)
+        if args.full:
+            t0 = time.perf_counter()
+            table_info = ctx.srs_precompute(srs, 0)
+            table_build_s = time.perf_counter() - t0
+            other = timed_msm(srs, scal, n, args.steps, args.warmup)
+            ctx.srs_precompute(srs, bp.SRS_TABLES_OFF)
     else:
-        other = timed_msm(srs, scal, n, args.steps, args.warmup)
+        if args.full:
+            other = timed_msm(srs, scal, n, args.steps, args.warmup)
         t0 = time.perf_counter()
         table_info = ctx.srs_precompute(srs, 0)
         table_build_s = time.perf_counter() - t0
     head = timed_msm(srs, scal, n, args.steps, args.warmup)
-    assert other["result"] == head["result"], "MSM with and without fixed-base tables disagree"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["result"])
     assert head["stats"]["tables"] == (not args.no_tables)
+
+    def finish():
+        emit(final=True)
+        if use_dist:
+            dist.barrier(group=ctl) if ctl is not None else dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:                   # a plain run: the headline leg only
+        checkpoint("weak_msm", elapsed=head["elapsed"])
+        finish()
+        return
+    assert other["result"] == head["result"], "MSM with and without fixed-base tables disagree"
     # the timed result against the closed form: points are (A0 + i D0) G, so the MSM is (sum_i s_i (A0 + i D0)) G -- one dot
     # product mod q, each rank's share computed where its scalars are (a wrong sum must not print a scaling number)
     weak_pairs = gather_objects(fr_sums(scal, n, rank * n))
@@ -1057,10 +1090,7 @@ def main():
             dist.barrier(group=ctl)
             checkpoint("one_proof_over_all_gpus")
 
-    emit(final=True)
-    if use_dist:
-        dist.barrier(group=ctl) if ctl is not None else dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -61,7 +61,7 @@ def test_bench_self_launches_two_ranks():
     relays rank 0's line.  gloo backend = a rehearsal of the N > 1 control flow on a 1-GPU box: barriers, max-over-ranks timing,
     the records' all-gather, both scaling legs, the rank-0 JSON line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "14", "--ntt-log-n", "14",
-           "--strong-log-n", "15", "--prove-log-n", "10", "--prove-reps", "2", "--backend", "gloo", "--skip-cpu"]
+           "--strong-log-n", "15", "--prove-log-n", "10", "--prove-reps", "2", "--backend", "gloo", "--skip-cpu", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -91,7 +91,7 @@ def test_bench_self_launches_two_ranks():
     assert grp["n_gpus"] == 2 and grp.get("same_proof_bytes_as_one_gpu") is True and grp["latency_ms_per_proof"] > 0, grp
     # the strong-scaling problem is the same for every N: one rank must get the same bytes
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log-n", "14", "--ntt-log-n", "14",
-                          "--strong-log-n", "15", "--prove-log-n", "0", "--skip-cpu", "--skip-seams", "--other-sizes"], capture_output=True, text=True,
+                          "--strong-log-n", "15", "--prove-log-n", "0", "--skip-cpu", "--skip-seams", "--other-sizes", "--full"], capture_output=True, text=True,
                          timeout=900, cwd=ROOT, env=env)
     assert one.returncode == 0, one.stdout[-2000:] + one.stderr[-2000:]
     line1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
@@ -103,7 +103,7 @@ def test_bench_keeps_the_finished_legs_when_a_rank_stops_taking_part():
     rank 0 runs into the next collective and stays there; the watchdog ends the ranks after --leg-timeout, the parent exits non-zero --
     and the COMPLETE lines of the legs that did finish (weak MSM, NTT) have been relayed and are what the caller keeps."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "14", "--ntt-log-n", "14",
-           "--strong-log-n", "15", "--prove-log-n", "0", "--backend", "gloo", "--skip-cpu", "--skip-group-legs", "--leg-timeout", "25",
+           "--strong-log-n", "15", "--prove-log-n", "0", "--backend", "gloo", "--skip-cpu", "--skip-group-legs", "--leg-timeout", "25", "--full",
            "--rehearse-hang-after", "ntt"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -129,7 +129,7 @@ def test_bench_under_launcher_with_rccl_single_rank():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16", "--ntt-log-n", "16", "--strong-log-n", "17",
-           "--prove-log-n", "0", "--skip-cpu", "--skip-seams", "--other-sizes"]
+           "--prove-log-n", "0", "--skip-cpu", "--skip-seams", "--other-sizes", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

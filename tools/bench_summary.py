@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""one-screen summary of a bench.py JSON line (file argument or stdin)"""
+"""one-screen summary of a `bench.py --full` JSON line (file argument or stdin)"""
 import json
 import sys
 

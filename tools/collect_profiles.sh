@@ -22,7 +22,7 @@ cd /tmp
   $R/tools/ubench_fr29 | grep -i "butterfl"
 } > $P/${TAG}_ubench_valu_floor.txt 2>&1
 # 1. the weak-scaling legs alone (2^20 MSM with and without tables + 2^20 NTT): msm_accumulate's average here is the bench line's kernel_ms
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt_weak -o b -- python3 $R/bench.py --steps 20 --warmup 5 --skip-cpu --prove-log-n 0 \
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt_weak -o b -- python3 $R/bench.py --full --steps 20 --warmup 5 --skip-cpu --prove-log-n 0 \
   --other-sizes --skip-seams --skip-pipelined --strong-log-n 0 > $P/${TAG}_bench_weak_under_rocprof.json 2> $O/${TAG}_kt_weak.err
 # 2. the 2^24 legs (strong scaling at N = 1: MSM with the auto table width + NTT)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt_strong -o b -- python3 $R/tools/run_msm.py --log-n 24 --reps 4 --tables 0 --ntt-log-n 24 \
@@ -50,5 +50,5 @@ python3 tools/pmc_traffic.py $P/${TAG}_pmc_f24_counter_collection.csv $P/${TAG}_
 grep "msm 2^\|ntt 2^" $O/${TAG}_kt_strong.log | tail -3
 # 5. the bench line of this commit, unprofiled, reading the files produced above once they are in profiles/
 cp $P/${TAG}_hbm_traffic.json $P/${TAG}_ubench_valu_floor.txt $R/profiles/ 2>/dev/null || true
-python3 bench.py > $P/${TAG}_bench_final.json 2> $O/${TAG}_bench_final.err
+python3 bench.py --full > $P/${TAG}_bench_final.json 2> $O/${TAG}_bench_final.err
 echo done

@@ -45,6 +45,7 @@ ERRORS = {
 }
 FR_BYTES_LE, FR_MONT = 0, 1
 MSM_BLOB_BYTES = 22592          # BP_MSM_BLOB_BYTES
+SRS_CHECK_SUBGROUP = 1          # BP_SRS_CHECK_SUBGROUP (bp_srs_load_compressed48 checks)
 COMM_ID_BYTES = 128             # BP_COMM_ID_BYTES (RCCL's ncclUniqueId)
 BASIS_LAGRANGE, BASIS_MONOMIAL = 0, 1
 
@@ -63,10 +64,13 @@ SIGNATURES = {
     "bp_synchronize": (_int, [_vp]),
     "bp_srs_load": (_int, [_vp, _vp, _sz, _pp(_u64)]),
     "bp_srs_load_projective144": (_int, [_vp, _vp, _sz, _pp(_u64)]),
+    "bp_srs_load_compressed48": (_int, [_vp, _vp, _sz, _u32, _pp(_u64), _pp(_sz)]),
+    "bp_srs_check_subgroup": (_int, [_vp, _u64, _sz, _sz, _pp(_sz)]),
     "bp_srs_generate": (_int, [_vp, _sz, _vp, _pp(_u64)]),
     "bp_srs_generate_progression": (_int, [_vp, _sz, _vp, _vp, _pp(_u64)]),
     "bp_srs_len": (_int, [_vp, _u64, _pp(_sz)]),
     "bp_srs_export": (_int, [_vp, _u64, _sz, _sz, _vp]),
+    "bp_srs_export_compressed48": (_int, [_vp, _u64, _sz, _sz, _vp]),
     "bp_srs_export_projective144": (_int, [_vp, _u64, _sz, _sz, _vp]),
     "bp_srs_free": (_int, [_vp, _u64]),
     "bp_srs_precompute": (_int, [_vp, _u64, _u32]),

@@ -112,6 +112,39 @@ class Context:
         self.check(self._lib.bp_srs_load_projective144(self._h, buf.ctypes.data, n, C.byref(h)), "bp_srs_load_projective144")
         return h.value
 
+    def srs_load_compressed48(self, points48, check_subgroup=True):
+        """n x 48 bytes in the compressed encoding (a ceremony file's records as they are), decoded on the GPU:
+        G1Affine::from_compressed, or from_compressed_unchecked with check_subgroup=False.  A rejected point raises
+        BpError(BP_ERR_BAD_POINT) whose text names the lowest failing index (also in the exception's `index`)"""
+        buf = points48 if isinstance(points48, np.ndarray) else np.frombuffer(bytes(points48), dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        n, h, bad = len(buf) // 48, C.c_uint64(), C.c_size_t()
+        rc = self._lib.bp_srs_load_compressed48(self._h, buf.ctypes.data, n, _lib.SRS_CHECK_SUBGROUP if check_subgroup else 0, C.byref(h),
+                                                C.byref(bad))
+        try:
+            self.check(rc, "bp_srs_load_compressed48")
+        except BpError as e:
+            e.index = bad.value if rc == -3 else None
+            raise
+        return h.value
+
+    def srs_export_compressed48(self, handle, first=0, n=None):
+        """points [first, first + n) in the 48-byte compressed encoding (G1Affine::to_compressed), encoded on the GPU"""
+        n = self.srs_len(handle) - first if n is None else n
+        out = np.zeros(48 * n, dtype=np.uint8)
+        self.check(self._lib.bp_srs_export_compressed48(self._h, handle, first, n, out.ctypes.data), "bp_srs_export_compressed48")
+        return bytes(out)
+
+    def srs_check_subgroup(self, handle, first=0, n=None):
+        """is_torsion_free over points [first, first + n) of any SRS, on the GPU: None, or the lowest index outside the subgroup"""
+        n = self.srs_len(handle) - first if n is None else n
+        bad = C.c_size_t()
+        rc = self._lib.bp_srs_check_subgroup(self._h, handle, first, n, C.byref(bad))
+        if rc == -3:
+            return bad.value
+        self.check(rc, "bp_srs_check_subgroup")
+        return None
+
     def msm_projective144(self, points144, scalars, fmt=FR_MONT):
         """BucketMSM::bucket_msm(&[G1Projective], &[Scalar]) in one call, nothing cached: upload in two pieces, multiply the first behind the upload of the second"""
         buf = points144 if isinstance(points144, np.ndarray) else np.frombuffer(bytes(points144), dtype=np.uint8)
@@ -680,8 +713,17 @@ class Setup:
         ctx = ctx or default_context()
         return Setup(ctx.srs_load(points96), ctx, tables)
 
+    @staticmethod
+    def from_compressed(points48, ctx=None, tables=True, check_subgroup=True):
+        """a ceremony's SRS: 48-byte compressed records, decoded (and by default subgroup-checked) on the GPU"""
+        ctx = ctx or default_context()
+        return Setup(ctx.srs_load_compressed48(points48, check_subgroup), ctx, tables)
+
     def powers_of_x(self):
         return self.ctx.srs_export(self.handle)
+
+    def powers_of_x_compressed(self):
+        return self.ctx.srs_export_compressed48(self.handle)
 
     def commit(self, polynomial):
         """setup.rs:32-37: asserts the Monomial basis, then bucket_msm over the whole SRS"""

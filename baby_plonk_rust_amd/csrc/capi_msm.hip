@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "g1_check.hpp"
 
 #include "capi_common.hpp"
 
@@ -56,23 +57,43 @@ static int srs_free_one(bp_ctx* ctx, uint64_t handle) {
   return BP_OK;
 }
 
+// bytes per host record of the SRS kinds that upload one (0, 1, 4)
+static size_t srs_record_bytes(int kind) { return kind == 0 ? 96 : kind == 1 ? 144 : 48; }
+// BP_ERR_BAD_POINT naming global point `index` and the reason of the status word (g1_check.hpp)
+static int srs_bad_point(bp_ctx* ctx, uint64_t index, uint32_t reason, size_t* first_bad) {
+  if (first_bad) *first_bad = (size_t)index;
+  char msg[160];
+  snprintf(msg, sizeof msg, "point %llu rejected: %s", (unsigned long long)index,
+           reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
+           : reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
+                                       : "not in the prime-order subgroup");
+  return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+}
+
 // One shard of an SRS on one device.  kind 0: decode 96-byte encodings, 1: normalise 144-byte projective images,
-// 2: generate tau^i G, 3: generate (a + i d) G.  src: this shard's slice of the host input (kinds 0, 1).
+// 2: generate tau^i G, 3: generate (a + i d) G, 4: decode 48-byte compressed encodings (+ the subgroup test when checks has
+// BP_SRS_CHECK_SUBGROUP; a rejected point's global index goes to *first_bad).  src: this shard's slice of the host input (kinds 0, 1, 4).
 static int srs_make_one(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a, const fr_t& d, size_t first, size_t n, size_t n_global,
-                        uint64_t* handle) {
+                        uint64_t* handle, uint32_t checks = 0, size_t* first_bad = nullptr) {
   DeviceGuard guard(ctx->device);
   g1_affine* d_pts = nullptr;
   BP_HIP(ctx, hipMalloc((void**)&d_pts, std::max<size_t>(n, 1) * sizeof(g1_affine)));
   int rc = BP_OK;
-  if (kind == 0 || kind == 1) {
-    const size_t rec = kind == 0 ? 96 : 144;
+  if (kind == 0 || kind == 1 || kind == 4) {
+    const size_t rec = srs_record_bytes(kind);
     uint8_t* d_bytes = nullptr;
     rc = ws_get(ctx, "io.bytes", n * rec, (void**)&d_bytes);
     if (rc == BP_OK && n) {
       hipError_t e = hipMemcpyAsync(d_bytes, src, n * rec, hipMemcpyHostToDevice, ctx->stream);
       if (e != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "SRS upload", e, __FILE__, __LINE__);
     }
-    if (rc == BP_OK) rc = kind == 0 ? srs_decode_run(ctx, d_bytes, n, d_pts) : srs_from_projective_run(ctx, (const g1_proj*)d_bytes, n, d_pts);
+    if (rc == BP_OK && kind == 4) {
+      uint64_t bad = ~0ull;
+      rc = srs_decode48_run(ctx, d_bytes, n, (checks & BP_SRS_CHECK_SUBGROUP) != 0, d_pts, &bad);
+      if (rc == BP_OK && bad != ~0ull) rc = srs_bad_point(ctx, first + (bad >> 2), (uint32_t)(bad & 3), first_bad);
+    } else if (rc == BP_OK) {
+      rc = kind == 0 ? srs_decode_run(ctx, d_bytes, n, d_pts) : srs_from_projective_run(ctx, (const g1_proj*)d_bytes, n, d_pts);
+    }
   } else {
     rc = srs_generate_run(ctx, a, d, kind == 2 ? 0 : 1, first, n, d_pts);
   }
@@ -87,16 +108,18 @@ static int srs_make_one(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a
   return srs_register(ctx, d_pts, n, first, n_global, handle);
 }
 
-// the whole SRS: one shard per member (contiguous point ranges), the leader's entry lists the members' handles
-static int srs_make(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a, const fr_t& d, size_t n, uint64_t* handle) {
+// the whole SRS: one shard per member (contiguous point ranges), the leader's entry lists the members' handles.
+// Shards are built in ascending order and the first failing one ends the build, so *first_bad (kind 4) is the lowest global index.
+static int srs_make(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a, const fr_t& d, size_t n, uint64_t* handle, uint32_t checks = 0,
+                    size_t* first_bad = nullptr) {
   const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const size_t rec = kind == 0 ? 96 : 144;
+  const size_t rec = srs_record_bytes(kind);
   std::vector<uint64_t> hs;
   for (size_t r = 0; r < sh.size(); r++) {
     size_t lo, hi;
     shard_range(n, r, sh.size(), &lo, &hi);
     uint64_t h = 0;
-    int rc = lift(ctx, sh[r], srs_make_one(sh[r], kind, src ? src + lo * rec : nullptr, a, d, lo, hi - lo, n, &h));
+    int rc = lift(ctx, sh[r], srs_make_one(sh[r], kind, src ? src + lo * rec : nullptr, a, d, lo, hi - lo, n, &h, checks, first_bad));
     if (rc != BP_OK) {
       for (size_t k = 0; k < hs.size(); k++) (void)srs_free_one(sh[k], hs[k]);
       return rc;
@@ -115,6 +138,11 @@ int bp_srs_load(bp_ctx* ctx, const uint8_t* points96, size_t n, uint64_t* srs_ha
 int bp_srs_load_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n, uint64_t* srs_handle) {
   if (!ctx || !srs_handle || (n && !points144)) return BP_ERR_INVALID_ARG;
   return srs_make(ctx, 1, points144, Fr::zero(), Fr::zero(), n, srs_handle);
+}
+int bp_srs_load_compressed48(bp_ctx* ctx, const uint8_t* points48, size_t n, uint32_t checks, uint64_t* srs_handle, size_t* first_bad) {
+  if (first_bad) *first_bad = SIZE_MAX;
+  if (!ctx || !srs_handle || (n && !points48) || (checks & ~BP_SRS_CHECK_SUBGROUP)) return BP_ERR_INVALID_ARG;
+  return srs_make(ctx, 4, points48, Fr::zero(), Fr::zero(), n, srs_handle, checks, first_bad);
 }
 
 static int srs_generate_common(bp_ctx* ctx, size_t n, const uint8_t a32[32], const uint8_t d32[32], int mode, uint64_t* handle) {
@@ -139,8 +167,8 @@ int bp_srs_len(bp_ctx* ctx, uint64_t srs_handle, size_t* n) {
   return BP_OK;
 }
 
-int bp_srs_export(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points96) {
-  if (!ctx || (n && !points96)) return BP_ERR_INVALID_ARG;
+// points [first, first + n) of every shard they lie on, encoded on the device: rec = 96 (to_uncompressed) or 48 (to_compressed)
+static int srs_export_bytes(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* out, size_t rec) {
   SrsEntry* lead;
   BP_TRY(srs_find(ctx, srs_handle, &lead));
   if (first > lead->n_global || n > lead->n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
@@ -153,10 +181,40 @@ int bp_srs_export(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint
     if (lo >= hi) continue;
     DeviceGuard guard(m->device);
     uint8_t* d_bytes;
-    BP_TRY(lift(ctx, m, ws_get(m, "io.bytes", (hi - lo) * 96, (void**)&d_bytes)));
-    BP_TRY(lift(ctx, m, srs_encode_run(m, e->d_points + (lo - e->first), hi - lo, d_bytes)));
-    BP_HIP(ctx, hipMemcpyAsync(points96 + (lo - first) * 96, d_bytes, (hi - lo) * 96, hipMemcpyDeviceToHost, m->stream));
+    BP_TRY(lift(ctx, m, ws_get(m, "io.bytes", (hi - lo) * rec, (void**)&d_bytes)));
+    const g1_affine* src = e->d_points + (lo - e->first);
+    BP_TRY(lift(ctx, m, rec == 96 ? srs_encode_run(m, src, hi - lo, d_bytes) : srs_encode48_run(m, src, hi - lo, d_bytes)));
+    BP_HIP(ctx, hipMemcpyAsync(out + (lo - first) * rec, d_bytes, (hi - lo) * rec, hipMemcpyDeviceToHost, m->stream));
     BP_HIP(ctx, stream_wait(m->stream));
+  }
+  return BP_OK;
+}
+int bp_srs_export(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points96) {
+  if (!ctx || (n && !points96)) return BP_ERR_INVALID_ARG;
+  return srs_export_bytes(ctx, srs_handle, first, n, points96, 96);
+}
+int bp_srs_export_compressed48(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points48) {
+  if (!ctx || (n && !points48)) return BP_ERR_INVALID_ARG;
+  return srs_export_bytes(ctx, srs_handle, first, n, points48, 48);
+}
+
+int bp_srs_check_subgroup(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, size_t* first_bad) {
+  if (first_bad) *first_bad = SIZE_MAX;
+  if (!ctx) return BP_ERR_INVALID_ARG;
+  SrsEntry* lead;
+  BP_TRY(srs_find(ctx, srs_handle, &lead));
+  if (first > lead->n_global || n > lead->n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
+  const std::vector<bp_ctx*> sh = shards_of(ctx);
+  for (size_t r = 0; r < sh.size(); r++) {            // shards in ascending point order: the first failing one holds the lowest index
+    bp_ctx* m = sh[r];
+    SrsEntry* e;
+    BP_TRY(lift(ctx, m, srs_find(m, member_handle(*lead, srs_handle, r), &e)));
+    const size_t lo = std::max(first, e->first), hi = std::min(first + n, e->first + e->n);
+    if (lo >= hi) continue;
+    DeviceGuard guard(m->device);
+    uint64_t bad = ~0ull;
+    BP_TRY(lift(ctx, m, srs_subgroup_run(m, e->d_points + (lo - e->first), hi - lo, &bad)));
+    if (bad != ~0ull) return srs_bad_point(ctx, lo + (bad >> 2), (uint32_t)(bad & 3), first_bad);
   }
   return BP_OK;
 }

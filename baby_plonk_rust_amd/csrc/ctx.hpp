@@ -297,6 +297,10 @@ int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, 
 int roots_run(bp_ctx* ctx, const fr_t& w, size_t n, fr_t* d_out);
 int srs_decode_run(bp_ctx* ctx, const uint8_t* d_bytes, size_t n, g1_affine* d_out);
 int srs_encode_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes);
+// compressed records (+ subgroup test) / subgroup test alone: *bad = ~0, or (lowest failing local index << 2) | reason (g1_check.hpp)
+int srs_decode48_run(bp_ctx* ctx, const uint8_t* d_bytes, size_t n, bool subgroup, g1_affine* d_out, uint64_t* bad);
+int srs_subgroup_run(bp_ctx* ctx, const g1_affine* d_pts, size_t n, uint64_t* bad);
+int srs_encode48_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes);
 int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affine* d_out);
 int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t first, size_t n, g1_affine* d_out);
 

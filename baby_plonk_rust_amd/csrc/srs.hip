@@ -25,6 +25,45 @@ int srs_encode_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_byte
   BP_HIP(ctx, hipGetLastError());
   return BP_OK;
 }
+// compressed records -> points (+ the subgroup test when `subgroup`); *bad = ~0 when every point passed, else the status word of
+// srs_kernels.hpp: (lowest failing index << 2) | reason, the index local to d_bytes
+static int status_begin(bp_ctx* ctx, unsigned long long** status) {
+  BP_TRY(ws_get(ctx, "srs.status64", 8, (void**)status));
+  BP_HIP(ctx, hipMemsetAsync(*status, 0xff, 8, ctx->stream));
+  return BP_OK;
+}
+static int status_read(bp_ctx* ctx, const unsigned long long* status, uint64_t* bad) {
+  BP_HIP(ctx, hipGetLastError());
+  unsigned long long h = ~0ull;
+  BP_HIP(ctx, hipMemcpyAsync(&h, status, 8, hipMemcpyDeviceToHost, ctx->stream));
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  *bad = h;
+  return BP_OK;
+}
+int srs_decode48_run(bp_ctx* ctx, const uint8_t* d_bytes, size_t n, bool subgroup, g1_affine* d_out, uint64_t* bad) {
+  *bad = ~0ull;
+  if (n == 0) return BP_OK;
+  unsigned long long* status;
+  BP_TRY(status_begin(ctx, &status));
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipLaunchKernelGGL(srs_decode48, grid, dim3(256), 0, ctx->stream, d_bytes, n, d_out, status);
+  if (subgroup) hipLaunchKernelGGL(srs_subgroup_check, grid, dim3(256), 0, ctx->stream, d_out, n, status);
+  return status_read(ctx, status, bad);
+}
+int srs_subgroup_run(bp_ctx* ctx, const g1_affine* d_pts, size_t n, uint64_t* bad) {
+  *bad = ~0ull;
+  if (n == 0) return BP_OK;
+  unsigned long long* status;
+  BP_TRY(status_begin(ctx, &status));
+  hipLaunchKernelGGL(srs_subgroup_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_pts, n, status);
+  return status_read(ctx, status, bad);
+}
+int srs_encode48_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(srs_encode48, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_in, n, d_bytes);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
 int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affine* d_out) {
   if (n == 0) return BP_OK;
   // points per inversion: 2^16 lanes (one wave per SIMD), 8..64 points each.  Measured at 2^20 points (load of the literal seam):

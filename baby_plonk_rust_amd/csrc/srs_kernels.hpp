@@ -3,9 +3,12 @@
 //   srs_encode96   : the inverse (G1Affine::to_uncompressed)
 //   srs_generate   : P_i = s_i * G with s_i = tau^i (Setup::generate_srs, setup.rs:12-31) or
 //                    s_i = a + i*d (synthetic benchmark points)
+//   srs_decode48 / srs_subgroup_check / srs_encode48 : the 48-byte compressed encoding (g1.rs:221-244, 326-390) and the subgroup
+//                    test (g1.rs:401-411), arithmetic in g1_check.hpp
 #pragma once
 #include "g1.hpp"
 #include "g1_28.hpp"
+#include "g1_check.hpp"
 
 namespace bp {
 
@@ -91,6 +94,47 @@ __global__ void __launch_bounds__(256) srs_encode96(const g1_affine* __restrict_
 #pragma unroll
   for (int j = 0; j < 24; j++)
     dst[j] = (uint32_t)buf[4 * j] | ((uint32_t)buf[4 * j + 1] << 8) | ((uint32_t)buf[4 * j + 2] << 16) | ((uint32_t)buf[4 * j + 3] << 24);
+}
+
+// ---- compressed points (round 7) ------------------------------------------------------------------------------------------------
+// One lane per point.  status: a 64-bit word the host sets to ~0; a failing lane does ONE atomicMin of (index << 2) | reason
+// (g1_check.hpp: 1 encoding, 2 not on the curve, 3 not in the subgroup), so one 8-byte read gives the lowest failing index and its
+// reason -- for the same index a decoding failure (1, 2) wins over the subgroup test, which sees the identity it leaves there.
+__device__ __forceinline__ void srs_report(unsigned long long* status, size_t i, uint32_t reason) {
+  atomicMin(status, ((unsigned long long)i << 2) | reason);
+}
+// G1Affine::from_compressed_unchecked (g1.rs:337-390): 48-byte records -> the device Montgomery affine form srs_decode96 writes
+__global__ void __launch_bounds__(256) srs_decode48(const uint8_t* __restrict__ in, size_t n, g1_affine* __restrict__ out,
+                                                     unsigned long long* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint4* src = reinterpret_cast<const uint4*>(in + 48 * i);          // 48 i is 16-byte aligned (in: a hipMalloc workspace)
+  uint32_t w[12];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const uint4 v = src[j];
+    w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
+  }
+  g1_affine p;
+  const uint32_t bad = g1_decode48(p, w);
+  if (bad) srs_report(status, i, bad);
+  out[i] = p;
+}
+// is_torsion_free (g1.rs:401-411) of resident points (the identity (0, 0) passes)
+__global__ void __launch_bounds__(256) srs_subgroup_check(const g1_affine* __restrict__ pts, size_t n, unsigned long long* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!g1_is_torsion_free(pts[i])) srs_report(status, i, G1_NOT_IN_SUBGROUP);
+}
+// G1Affine::to_compressed (g1.rs:221-244): the compressed twin of srs_encode96
+__global__ void __launch_bounds__(256) srs_encode48(const g1_affine* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[12];
+  g1_encode48(w, in[i]);
+  uint4* dst = reinterpret_cast<uint4*>(out + 48 * i);
+#pragma unroll
+  for (int j = 0; j < 3; j++) dst[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
 }
 
 // G1Projective memory images (x | y | z Montgomery limbs, g1.rs:442-446) -> affine, the device side of

@@ -127,6 +127,7 @@ struct Scalar {
 enum class Basis { Lagrange = BP_BASIS_LAGRANGE, Monomial = BP_BASIS_MONOMIAL };   // polynomial.rs:8-11
 
 using G1 = std::array<uint8_t, 96>;   // G1Affine::to_uncompressed (g1.rs:246-260)
+using G1Compressed = std::array<uint8_t, 48>;   // G1Affine::to_compressed (g1.rs:221-244)
 
 // src/utils.rs:39-43
 inline Scalar root_of_unity(uint64_t group_order) {
@@ -283,6 +284,25 @@ class Setup {
     c.check(bp_srs_load(c.raw(), points.empty() ? nullptr : points[0].data(), points.size(), &h), "from_points");
     if (tables) (void)bp_srs_precompute(c.raw(), h, 0);
     return Setup(h, c);
+  }
+  // a ceremony's SRS as its file stores it: 48-byte compressed records (G1Affine::to_compressed), decoded on the GPU --
+  // G1Affine::from_compressed, or from_compressed_unchecked with check_subgroup = false.  A rejected record is a Panic naming its index.
+  static Setup from_compressed(const std::vector<G1Compressed>& points48, Context& c = Context::global(), bool tables = true,
+                               bool check_subgroup = true) {
+    uint64_t h = 0;
+    size_t bad = 0;
+    c.check(bp_srs_load_compressed48(c.raw(), points48.empty() ? nullptr : points48[0].data(), points48.size(),
+                                     check_subgroup ? BP_SRS_CHECK_SUBGROUP : 0u, &h, &bad),
+            "from_compressed");
+    if (tables) (void)bp_srs_precompute(c.raw(), h, 0);
+    return Setup(h, c);
+  }
+  std::vector<G1Compressed> powers_of_x_compressed() const {
+    size_t n = 0;
+    ctx_->check(bp_srs_len(ctx_->raw(), handle_, &n), "srs_len");
+    std::vector<G1Compressed> out(n);
+    if (n) ctx_->check(bp_srs_export_compressed48(ctx_->raw(), handle_, 0, n, out[0].data()), "srs_export_compressed48");
+    return out;
   }
   // Setup::commit over ALL ranks of the context's communicator: `slice` holds the coefficients of this rank's point range; every rank
   // receives the same commitment (bp_msm_g1_allgather: one ncclAllGather of the ranks' partial-sum records under the C ABI)

@@ -106,6 +106,21 @@ int  bp_srs_load(bp_ctx* ctx, const uint8_t* points96, size_t n, uint64_t* srs_h
  * G1Projective::batch_normalize does on the host, g1.rs:806-839); z = 0 is the identity.  No curve check: the type
  * guarantees it (as G1Affine::from(&G1Projective) assumes). */
 int  bp_srs_load_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n, uint64_t* srs_handle);
+/* A ceremony's SRS: n points in the 48-byte compressed encoding (G1Affine::to_compressed, g1.rs:221-244), decoded on the GPU.
+ * checks = BP_SRS_CHECK_SUBGROUP: G1Affine::from_compressed (g1.rs:326-331); checks = 0: from_compressed_unchecked (g1.rs:337-390).
+ * A record is rejected when its compression flag is clear, the masked x is >= p, the infinity flag is set with x != 0 or with the sort
+ * flag, x^3 + 4 has no square root, or (checked) the point lies outside the prime-order subgroup (is_torsion_free, g1.rs:401-411).
+ * y is chosen by lexicographically_largest() ^ sort flag; the identity is 0xc0 then zeros.  Any rejection is BP_ERR_BAD_POINT:
+ * first_bad (may be NULL) receives the lowest failing global index, bp_last_error names it and the reason (encoding / not on the
+ * curve / not in the subgroup), and no handle is created.  On success *first_bad = SIZE_MAX.  Sharded like bp_srs_load on
+ * bp_init_multi contexts; n == 0 behaves as bp_srs_load with n == 0.  Unlike the reference (CtOption, constant time) the GPU code is
+ * variable-time: SRS points are public. */
+#define BP_SRS_CHECK_SUBGROUP 1u
+int  bp_srs_load_compressed48(bp_ctx* ctx, const uint8_t* points48, size_t n, uint32_t checks, uint64_t* srs_handle, size_t* first_bad);
+/* is_torsion_free (g1.rs:401-411) of points [first, first+n) of any SRS, on the GPU: what from_uncompressed adds to bp_srs_load's
+ * checks.  BP_OK with *first_bad = SIZE_MAX, or BP_ERR_BAD_POINT with the lowest global index outside the subgroup in *first_bad
+ * (may be NULL) and in bp_last_error. */
+int  bp_srs_check_subgroup(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, size_t* first_bad);
 /* The same seam as ONE call, nothing cached: result = sum_i scalars[i] * points[i] over min(n_points, n_scalars) pairs (the zip of
  * msm.rs:85), both operands in host memory.  Equivalent to bp_srs_load_projective144 + bp_msm_g1 + bp_srs_free, but the operands cross
  * PCIe in two pieces and the multiplication of the first runs while the second is uploaded and normalised, out of workspaces instead
@@ -120,6 +135,8 @@ int  bp_srs_generate_progression(bp_ctx* ctx, size_t n, const uint8_t a32[32], c
 int  bp_srs_len(bp_ctx* ctx, uint64_t srs_handle, size_t* n);
 /* Read points [first, first+n) back in the 96-byte encoding (G1Affine::to_uncompressed). */
 int  bp_srs_export(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points96);
+/* The same points in the 48-byte compressed encoding (G1Affine::to_compressed, g1.rs:221-244), encoded on the GPU. */
+int  bp_srs_export_compressed48(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points48);
 /* The same points as G1Projective memory images (z = 1, the identity as (0 : 1 : 0)): G1Projective::from(&G1Affine), g1.rs:176-190. */
 int  bp_srs_export_projective144(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points144);
 int  bp_srs_free(bp_ctx* ctx, uint64_t srs_handle);

@@ -1,0 +1,20 @@
+"""-m gpu: builds and runs tests/cpp/test_srs_compressed.cpp (Setup::from_compressed of host/baby_plonk.hpp) against libbp_msm_ntt.so"""
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_cpp_setup_from_compressed(tmp_path):
+    exe = str(tmp_path / "test_srs_compressed")
+    libdir = os.path.join(ROOT, "baby_plonk_rust_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "test_srs_compressed.cpp"), "-o", exe,
+                           "-L" + libdir, "-lbp_msm_ntt", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    golden = os.path.join(ROOT, "tests", "golden")
+    out = subprocess.run([exe, os.path.join(golden, "g1_compressed_valid_test_vectors.dat"), os.path.join(golden, "g1_uncompressed_valid_test_vectors.dat")],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "srs compressed ok" in out.stdout

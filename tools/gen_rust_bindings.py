@@ -88,7 +88,7 @@ def generate():
             continue
         seen.add(name)
         ty = "c_int" if value < 0 or value < 2**31 else "u64"
-        if name in ("BP_SRS_TABLES_OFF",):
+        if name in ("BP_SRS_TABLES_OFF", "BP_SRS_CHECK_SUBGROUP"):         # flags of u32 parameters
             ty = "u32"
         if name.endswith("_BYTES"):
             ty = "usize"

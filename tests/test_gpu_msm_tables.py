@@ -13,6 +13,7 @@ from tests import bigint_model as M
 from tests.gpu_common import NTHREADS, Q, closed_form, experiment, oracle_dot, progression_bytes
 
 pytestmark = pytest.mark.gpu
+P_MOD = M.P
 HERE = os.path.dirname(__file__)
 UNCOMP = open(os.path.join(HERE, "golden", "g1_uncompressed_valid_test_vectors.dat"), "rb").read()
 
@@ -468,4 +469,40 @@ def test_table_memory_budget(ctx):
         assert ctx.srs_table_info(h)["window_bits"] == 16
     finally:
         hook(ctx._h, 0)
+    ctx.srs_free(h)
+
+
+def _mont_scalars(vals):
+    return np.frombuffer(b"".join((v % Q * (1 << 256) % Q).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+@pytest.mark.parametrize("c,log_n", [(0, 12), (11, 12), (21, 18)])
+def test_adversarial_points_small_multiples_and_their_negatives(ctx, c, log_n):
+    """The other edge tests vary the SCALARS over an SRS of generic points.  Here the POINTS are adversarial: 64 distinct points only -- k G and
+    -k G for k = 1..32 -- repeated in shuffled order, so that a bucket keeps meeting the point it already holds (P + P), its negative (P - P)
+    and running sums that pass through the identity in mid-bucket.  One case per path: no tables (c = 0), tables with power-of-two windows,
+    tables with radix-R digits (21 bits).  Checked against the closed form (sum_i s_i k_i) G on Python integers."""
+    rnd = random.Random(0xAD5E + 100 * c + log_n)
+    n = (1 << log_n) + 21
+    pool_k = list(range(1, 33)) + [-k for k in range(1, 33)]
+    pos = [M.ec_mul(k) for k in range(1, 33)]
+    pool = np.stack([np.frombuffer(M.enc96(p), dtype=np.uint8) for p in pos + [(p[0], P_MOD - p[1]) for p in pos]])
+    idx = [rnd.randrange(64) for _ in range(n)]
+    ks = [pool_k[i] for i in idx]
+    h = ctx.srs_load(pool[idx].tobytes())
+    if c:
+        assert ctx.srs_precompute(h, c)["window_bits"] == c
+    few = [rnd.randrange(Q) for _ in range(3)] + [1, Q - 1, 2, (Q - 1) // 2]
+    uni = [rnd.randrange(Q) for _ in range(n)]
+    same = [few[0]] * n                                             # every window of every scalar the same digit: each bucket holds +-k G only
+    mixed = [rnd.choice(few) if i % 2 else uni[i] for i in range(n)]
+    cancel = list(mixed)                                            # the whole sum is the identity
+    cancel[-1] = -sum(s * k for s, k in zip(mixed[:-1], ks[:-1])) * pow(ks[-1], -1, Q) % Q
+    for name, sc in (("same", same), ("mixed", mixed), ("uniform", uni), ("cancel", cancel), ("ones", [1] * n)):
+        want = M.enc96(M.ec_mul(sum(s * k for s, k in zip(sc, ks)) % Q))
+        assert ctx.msm(h, _mont_scalars(sc)) == want, (c, log_n, name)
+        assert bool(ctx.msm_stats()["tables"]) == bool(c), (c, name)
+        if c:
+            assert ctx.msm_stats()["window_bits"] == c
+    assert ctx.msm(h, _mont_scalars(cancel)) == M.enc96(None)
     ctx.srs_free(h)

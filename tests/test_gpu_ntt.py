@@ -140,3 +140,79 @@ def test_async_transforms_back_to_back(ctx):
     assert st["device_ms"] > 0 and st["passes"] == 2
     ctx.ntt_device(t.data_ptr(), 14, inverse=True)               # a blocking call after enqueued ones
     assert (t.cpu().numpy().view(np.uint64).reshape(-1, 4) == x).all()
+
+
+# ---- closed-form vectors through the multi-pass kernels ------------------------------------------------------------------------------
+# Random data never makes a butterfly difference exactly zero, never walks a sum along the 2q boundary of the lazy representation and
+# never leaves a whole pass with a single non-zero row.  These vectors do, and their transforms are known in closed form, so the
+# expected values are Python integers (pow), not the oracle.
+R256 = 1 << 256
+
+
+def _mont_rows(vals):
+    """Python integers -> the Montgomery limbs the library computes on, [len, 4] u64"""
+    return np.frombuffer(b"".join((v % Q * R256 % Q).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def _power_table(n, inverse):
+    """row e = omega^e (forward) or omega^-e / n (inverse), e < n"""
+    w = M.omega(n)
+    v, out = 1, []
+    if inverse:
+        w, v = M.inv(w, Q), M.inv(n, Q)
+    for _ in range(n):
+        out.append(v)
+        v = v * w % Q
+    return _mont_rows(out)
+
+
+@pytest.mark.parametrize("logn", [13, 14, 15, 16, 17, 18, 20])
+def test_multi_pass_closed_form_vectors(ctx, logn):
+    n = 1 << logn
+    rnd = random.Random(0xC105ED + logn)
+    c = rnd.randrange(1, Q)
+    # impulses: index n - 1, and 2^b - 1 and 2^b for EVERY bit b, so both sides of every pass boundary whatever the split of the passes
+    ks = [n - 1, 1, 3] + [(1 << b) - 1 for b in range(2, logn)] + [1 << b for b in range(1, logn)] + [rnd.randrange(n)]
+    j = np.arange(n, dtype=np.int64)
+    for inverse in (False, True):
+        tab = _power_table(n, inverse)
+        scale = M.inv(n, Q) if inverse else 1
+        cols, want = [], []
+
+        def column(nonzero, expect_rows):
+            x = np.zeros((n, 4), dtype=np.uint64)
+            for i, v in nonzero:
+                x[i] = v
+            cols.append(x)
+            want.append(expect_rows)
+
+        def sparse(rows):
+            y = np.zeros((n, 4), dtype=np.uint64)
+            for i, v in rows:
+                y[i] = _mont_rows([v])[0]
+            return y
+
+        for cc in (c, Q - 1, 1):                                  # constant vectors: n c (or c) at index 0, zero elsewhere
+            cols.append(np.tile(_mont_rows([cc]), (n, 1)))
+            want.append(sparse([(0, cc * n * scale)]))
+        alt = np.zeros((n, 4), dtype=np.uint64)                    # (0, q-1, 0, q-1, ...): (q-1) n/2 at 0 and n/2 at n/2 (omega^(n/2) = -1)
+        alt[1::2] = _mont_rows([Q - 1])[0]
+        cols.append(alt)
+        want.append(sparse([(0, (Q - 1) * (n // 2) * scale), (n // 2, (n // 2) * scale)]))
+        one, minus_one = _mont_rows([1])[0], _mont_rows([Q - 1])[0]
+        for i, k in enumerate(ks):                                 # impulse at k: omega^(+-jk) (/ n); with value q - 1: the same shifted by n/2
+            if i % 4 == 3:
+                column([(k, minus_one)], tab[(j * k + n // 2) % n])
+            else:
+                column([(k, one)], tab[(j * k) % n])
+        while len(cols) % 8:
+            cols.append(np.zeros((n, 4), dtype=np.uint64))
+            want.append(np.zeros((n, 4), dtype=np.uint64))
+        # one column at a time for the first few, then batches of eight
+        for b in range(4):
+            got = bp.i_ntt_381(cols[b], ctx) if inverse else bp.ntt_381(cols[b], ctx)
+            assert (got == want[b]).all(), (logn, inverse, "single column", b)
+        for b in range(0, len(cols), 8):
+            got = ctx.ntt_batch(np.stack(cols[b:b + 8]), inverse=inverse)
+            for i in range(8):
+                assert (got[i] == want[b + i]).all(), (logn, inverse, "batch of eight", b + i, np.nonzero((got[i] != want[b + i]).any(axis=1))[0][:4])

@@ -84,6 +84,9 @@ SIGNATURES = {
     "bp_prove": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "bp_prove_last_stats": (_int, [_vp, _vp, _pp(C.c_float)]),
     "bp_transcript_test_vector": (_int, [_vp]),
+    "bp_plonk_challenges": (_int, [_vp, _sz, _int, _vp, _pp(_sz)]),
+    "bp_verify_reduce": (_int, [_vp, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _int, _vp, _pp(_sz)]),
+    "bp_verify_last_stats": (_int, [_vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

@@ -342,6 +342,50 @@ class Context:
         """fill HBM at `ptr` with n synthetic Montgomery scalars (the same stream the CPU baseline uses)"""
         self.check(self._lib.bp_fr_synthetic_device(self._h, ptr, n, seed), "bp_fr_synthetic_device")
 
+    def verify_reduce(self, log_n, vk, proofs, public_inputs=None, weights=None, challenges=None, fmt=FR_MONT):
+        """Verifier::verify (verifier.rs:80-192) of m proofs of one circuit up to the two pairings (bp_verify_reduce): returns
+        (A96, B96); the batch is valid iff pairing(A, x_2) == pairing(B, G2 generator).  vk: the 768 bytes of
+        Circuit.commitments (or that dict); proofs: m x 624 bytes (bytes, or a list of proofs); public_inputs: [m, n_public]
+        scalars, row j = the vector handed to verify() for proof j; weights: m scalars drawn AFTER the proofs were received
+        (None: a single proof, weight 1); challenges: None = the reference's transcript on the device, else [m, 6] scalars
+        beta gamma alpha zeta nu mu.  Scalars: [.., 4] uint64 Montgomery limbs (fmt=FR_MONT) or [.., 32] uint8 canonical
+        little-endian bytes (fmt=FR_BYTES_LE).  A rejected proof raises BpError whose `index` is the lowest failing proof."""
+        if isinstance(vk, dict):
+            vk = b"".join(vk[k] for k in CIRCUIT_COLUMNS)
+        vkb = np.frombuffer(bytes(vk), dtype=np.uint8).copy()
+        if len(vkb) != 768:
+            raise BpError(-1, "verify_reduce", "vk: eight 96-byte commitments expected")
+        rec, m = _proof_records(proofs)
+
+        def scalars(a, per_proof, what):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(a, dtype=np.uint64 if fmt == FR_MONT else np.uint8)
+            width = 4 if fmt == FR_MONT else 32
+            if a.size % width or (a.size // width) % max(m, 1) or (per_proof is not None and a.size != m * per_proof * width):
+                raise BpError(-6, "verify_reduce", "%s: %d scalars do not fit %d proofs" % (what, a.size // width, m))
+            return a, (a.size // width // m if m else 0)
+        pub, n_public = scalars(public_inputs, None, "public_inputs")
+        w, _ = scalars(weights, 1, "weights")
+        ch, _ = scalars(challenges, 6, "challenges")
+        out, bad = np.zeros(192, dtype=np.uint8), C.c_size_t()
+        rc = self._lib.bp_verify_reduce(self._h, log_n, vkb.ctypes.data, rec.ctypes.data if m else None, m,
+                                        pub.ctypes.data if pub is not None and pub.size else None, n_public,
+                                        None if w is None else w.ctypes.data, None if ch is None else ch.ctypes.data, fmt,
+                                        out.ctypes.data, C.byref(bad))
+        try:
+            self.check(rc, "bp_verify_reduce")
+        except BpError as e:
+            e.index = bad.value if rc in (-3, -4) and bad.value != C.c_size_t(-1).value else None
+            raise
+        return out[:96].tobytes(), out[96:].tobytes()
+
+    def verify_stats(self):
+        """HIP-event milliseconds of the five stages of the last verify_reduce"""
+        ms = (C.c_float * 5)()
+        self.check(self._lib.bp_verify_last_stats(self._h, ms), "bp_verify_last_stats")
+        return dict(zip(("upload_ms", "transcript_ms", "scalars_ms", "decode_check_ms", "msm_ms"), [float(v) for v in ms]))
+
     def set_stream(self, stream_ptr):
         self.check(self._lib.bp_set_stream(self._h, stream_ptr), "bp_set_stream")
 
@@ -824,3 +868,46 @@ def transcript_test_vector():
     if rc:
         raise BpError(rc, "bp_transcript_test_vector", "")
     return bytes(out)
+
+
+def _proof_records(proofs):
+    """bytes of m x 624, or a list of 624-byte proofs -> (uint8 array, m)"""
+    if isinstance(proofs, (list, tuple)):
+        proofs = b"".join(bytes(p) for p in proofs)
+    rec = proofs if isinstance(proofs, np.ndarray) else np.frombuffer(bytes(proofs), dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint8).reshape(-1)
+    if len(rec) % 624:
+        raise BpError(-6, "proofs", "a multiple of 624 bytes expected")
+    return rec, len(rec) // 624
+
+
+def plonk_challenges(proofs, fmt=FR_MONT):
+    """Verifier::compute_challengs (verifier.rs:193-209) of m proofs on the host (bp_plonk_challenges, no GPU): [m, 6, 4] uint64
+    Montgomery limbs, or [m, 6, 32] canonical little-endian bytes with fmt=FR_BYTES_LE; order beta gamma alpha zeta nu mu.
+    An evaluation >= q raises BpError(BP_ERR_BAD_SCALAR) with the record in `index`."""
+    rec, m = _proof_records(proofs)
+    out = np.zeros((m, 6, 4), dtype=np.uint64) if fmt == FR_MONT else np.zeros((m, 6, 32), dtype=np.uint8)
+    bad = C.c_size_t()
+    rc = _lib.load().bp_plonk_challenges(rec.ctypes.data if m else None, m, fmt, out.ctypes.data if m else None, C.byref(bad))
+    if rc:
+        e = BpError(rc, "bp_plonk_challenges", "evaluation >= q in record %d" % bad.value if rc == -4 else "")
+        e.index = bad.value if rc == -4 else None
+        raise e
+    return out
+
+
+class Verifier:
+    """src/verifier.rs:41-79: the verifier's preprocessed input (the eight commitments of Circuit.commitments) for a batch of
+    proofs of that circuit.  The G2 side (x_2) and the pairings stay with the host: pairing_inputs returns the two G1 points
+    (A, B) with  batch valid  <=>  pairing(A, x_2) == pairing(B, G2Affine::generator())  (verifier.rs:187-191)."""
+
+    def __init__(self, setup, circuit):
+        assert setup.ctx is circuit.ctx
+        self.ctx, self.group_order = setup.ctx, circuit.group_order
+        self.commitments = circuit.commitments(setup)
+        self.vk = b"".join(self.commitments[k] for k in CIRCUIT_COLUMNS)
+
+    def pairing_inputs(self, proofs, public_inputs, weights=None, challenges=None, fmt=FR_MONT):
+        """proofs: m x 624 bytes; public_inputs: [m, n_public] scalars (None: no public inputs); weights: m scalars the caller drew
+        after it received the proofs, >= 128 bits of entropy each (None for a single proof)."""
+        return self.ctx.verify_reduce(self.group_order.bit_length() - 1, self.vk, proofs, public_inputs, weights, challenges, fmt)

@@ -1,0 +1,237 @@
+// capi_verify.hip -- C ABI, part 7: batch verification.  bp_verify_reduce turns m proofs of one circuit into the two G1 points whose
+// pairings decide the batch (Verifier::verify, src/verifier.rs:80-192, without its last line); bp_plonk_challenges is the verifier's
+// transcript (compute_challengs, verifier.rs:193-209) on the host.  Kernels: verify_kernels.hpp; decoding and the subgroup test are
+// the SRS loader's (srs.hip), both multiplications the table-free MSM over workspace points (msm.hip).
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ctx.hpp"
+#include "g1_check.hpp"
+#include "verify_kernels.hpp"
+
+#include "capi_common.hpp"
+
+using namespace bp;
+
+static const char* const VERIFY_POINT_NAME[VERIFY_POINTS] = {"a_1", "b_1", "c_1", "z_1", "t_lo_1", "t_mid_1", "t_hi_1", "w_zeta_1", "w_zeta_omega_1"};
+static const char* const VERIFY_EVAL_NAME[VERIFY_EVALS] = {"a_bar", "b_bar", "c_bar", "s1_bar", "s2_bar", "z_omega_bar"};
+
+static bool eval_canonical(const uint8_t* b32) {
+  fr_t v, t;
+  memcpy(&v, b32, 32);
+  return big_sub(t, v, Fr::modulus()) != 0;
+}
+
+int bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void* out, size_t* first_bad) {
+  if (!fmt_ok(scalar_fmt) || (m && (!proofs624 || !out))) return BP_ERR_INVALID_ARG;
+  if (first_bad) *first_bad = SIZE_MAX;
+  for (size_t j = 0; j < m; j++) {
+    const uint8_t* rec = proofs624 + (size_t)VERIFY_RECORD_BYTES * j;
+    for (int k = 0; k < VERIFY_EVALS; k++)
+      if (!eval_canonical(rec + 432 + 32 * k)) {
+        if (first_bad) *first_bad = j;
+        return BP_ERR_BAD_SCALAR;
+      }
+    uint32_t words[VERIFY_RECORD_WORDS];
+    memcpy(words, rec, VERIFY_RECORD_BYTES);
+    fr_t c[6];
+    plonk_challenges(words, c, nullptr);
+    for (int k = 0; k < 6; k++) {
+      fr_t v = c[k];
+      if (scalar_fmt == BP_FR_MONT) Fr::to_mont(v, c[k]);
+      memcpy((uint8_t*)out + ((size_t)6 * j + k) * 32, &v, 32);
+    }
+  }
+  return BP_OK;
+}
+
+// one vk commitment: canonical, flags, on the curve (the checks of bp_srs_load); the identity is (0, 0)
+static bool vk_point_decode(g1_affine& out, const uint8_t in96[96]) {
+  g1_proj p;
+  if (!host_decode96(p, in96)) return false;
+  if (g1_is_identity(p)) {
+    out.x = Fp::zero();
+    out.y = Fp::zero();
+    return true;
+  }
+  fp_t lhs, rhs, b4 = Fp::one();
+  Fp::sqr(lhs, p.y);
+  Fp::sqr(rhs, p.x);
+  Fp::mul(rhs, rhs, p.x);
+  Fp::dbl(b4, b4);
+  Fp::dbl(b4, b4);
+  Fp::add(rhs, rhs, b4);
+  if (!big_eq(lhs, rhs)) return false;
+  out.x = p.x;
+  out.y = p.y;
+  return true;
+}
+
+static void encode_identity_pair(uint8_t out192[192]) {
+  memset(out192, 0, 192);
+  out192[0] = out192[96] = 0x40;
+}
+
+static int verify_events(bp_ctx* ctx) {
+  for (auto& e : ctx->verify_ev)
+    if (!e) BP_HIP(ctx, hipEventCreate(&e));
+  return BP_OK;
+}
+
+static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                             size_t n_public, const void* weights, const void* challenges, int fmt, uint8_t out192[192], size_t* first_bad) {
+  // the nine shared bases: eight vk commitments in the order bp_circuit_commitments writes them, then G
+  g1_affine shared_pts[VERIFY_SHARED];
+  for (int k = 0; k < 8; k++)
+    if (!vk_point_decode(shared_pts[k], vk768 + 96 * k)) {
+      char msg[96];
+      snprintf(msg, sizeof msg, "verifier key: commitment %d rejected (encoding, flags or not on the curve)", k);
+      return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+    }
+  shared_pts[8] = g1_affine_generator();
+  VerifyParams P;
+  if (!host_root_of_unity(P.omega, (uint64_t)1 << log_n)) return BP_ERR_INVALID_ARG;
+  {
+    fr_t n = Fr::zero();
+    n.l[log_n >> 5] = 1u << (log_n & 31);
+    Fr::to_mont(n, n);
+    fr_invert(P.n_inv, n);
+  }
+  P.log_n = log_n;
+  P.fmt = fmt;
+  P.chal_fmt = challenges ? fmt : BP_FR_MONT;
+  P.n_public = n_public;
+
+  const size_t n_pts = (size_t)VERIFY_POINTS * m, n_all = n_pts + VERIFY_SHARED;
+  uint8_t *d_rec, *d_comp;
+  fr_t *d_chal, *d_w = nullptr, *d_pub = nullptr, *d_b, *d_a, *d_sh;
+  g1_affine* d_pts;
+  g1_affine28* d_p28;
+  unsigned long long* d_status;
+  BP_TRY(ws_get(ctx, "verify.records", m * VERIFY_RECORD_BYTES, (void**)&d_rec));
+  BP_TRY(ws_get(ctx, "verify.comp", n_pts * 48, (void**)&d_comp));
+  BP_TRY(ws_get(ctx, "verify.chal", m * 6 * sizeof(fr_t), (void**)&d_chal));
+  if (weights) BP_TRY(ws_get(ctx, "verify.weights", m * sizeof(fr_t), (void**)&d_w));
+  BP_TRY(ws_get(ctx, "verify.public", m * n_public * sizeof(fr_t), (void**)&d_pub));
+  BP_TRY(ws_get(ctx, "verify.scal_b", n_all * sizeof(fr_t), (void**)&d_b));
+  BP_TRY(ws_get(ctx, "verify.scal_a", 2 * m * sizeof(fr_t), (void**)&d_a));
+  BP_TRY(ws_get(ctx, "verify.shared", n_pts * sizeof(fr_t), (void**)&d_sh));
+  BP_TRY(ws_get(ctx, "verify.points", n_all * sizeof(g1_affine), (void**)&d_pts));
+  BP_TRY(ws_get(ctx, "verify.p28", n_all * sizeof(g1_affine28), (void**)&d_p28));
+  BP_TRY(ws_get(ctx, "verify.status", 8, (void**)&d_status));
+  BP_TRY(verify_events(ctx));
+  hipStream_t st = ctx->stream;
+  hipEvent_t* ev = ctx->verify_ev;
+
+  // stage 0: upload (pageable host memory: the copies are staged by the runtime before they return)
+  BP_HIP(ctx, hipEventRecord(ev[0], st));
+  BP_HIP(ctx, hipMemcpyAsync(d_rec, proofs624, m * VERIFY_RECORD_BYTES, hipMemcpyHostToDevice, st));
+  if (challenges) BP_HIP(ctx, hipMemcpyAsync(d_chal, challenges, m * 6 * sizeof(fr_t), hipMemcpyHostToDevice, st));
+  if (weights) BP_HIP(ctx, hipMemcpyAsync(d_w, weights, m * sizeof(fr_t), hipMemcpyHostToDevice, st));
+  if (n_public) BP_HIP(ctx, hipMemcpyAsync(d_pub, public_inputs, m * n_public * sizeof(fr_t), hipMemcpyHostToDevice, st));
+  BP_HIP(ctx, hipMemcpyAsync(d_pts + n_pts, shared_pts, sizeof shared_pts, hipMemcpyHostToDevice, st));
+  BP_HIP(ctx, hipMemsetAsync(d_status, 0xff, 8, st));
+  // stage 1: transcript
+  BP_HIP(ctx, hipEventRecord(ev[1], st));
+  if (!challenges) {
+    hipLaunchKernelGGL(verify_transcript, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, d_rec, m, d_chal);
+    BP_HIP(ctx, hipGetLastError());
+  }
+  // stage 2: scalars
+  BP_HIP(ctx, hipEventRecord(ev[2], st));
+  hipLaunchKernelGGL(verify_scalars, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, st, d_rec, m, d_chal, d_w, d_pub, P, d_b, d_a, d_sh, d_status);
+  BP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(verify_shared_sum, dim3(VERIFY_SHARED), dim3(256), 0, st, d_sh, m, d_b + n_pts);
+  BP_HIP(ctx, hipGetLastError());
+  unsigned long long scalar_bad = ~0ull;
+  BP_HIP(ctx, hipMemcpyAsync(&scalar_bad, d_status, 8, hipMemcpyDeviceToHost, st));
+  // stage 3: decode + subgroup check (the call waits for the stream and reads the status word)
+  BP_HIP(ctx, hipEventRecord(ev[3], st));
+  hipLaunchKernelGGL(verify_gather, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, st, d_rec, m, d_comp);
+  BP_HIP(ctx, hipGetLastError());
+  uint64_t point_bad = ~0ull;
+  BP_TRY(srs_decode48_run(ctx, d_comp, n_pts, true, d_pts, &point_bad));
+  BP_HIP(ctx, hipEventRecord(ev[4], st));
+
+  if (point_bad != ~0ull || scalar_bad != ~0ull) {
+    // The status word of the decoder is the lowest COLUMN-MAJOR index; the lowest proof may sit in a later column.  A rejection is
+    // the rare path: ask column by column (nine short runs over data already decoded once) and keep the lowest proof.
+    size_t pt_proof = SIZE_MAX;
+    uint32_t pt_field = 0, pt_reason = 0;
+    if (point_bad != ~0ull)
+      for (int k = 0; k < VERIFY_POINTS; k++) {
+        uint64_t bad = ~0ull;
+        BP_TRY(srs_decode48_run(ctx, d_comp + (size_t)k * m * 48, m, true, d_pts + (size_t)k * m, &bad));
+        if (bad != ~0ull && (size_t)(bad >> 2) < pt_proof) {
+          pt_proof = (size_t)(bad >> 2);
+          pt_field = (uint32_t)k;
+          pt_reason = (uint32_t)(bad & 3);
+        }
+      }
+    const size_t sc_proof = scalar_bad == ~0ull ? SIZE_MAX : (size_t)(scalar_bad >> 4);
+    char msg[200];
+    if (pt_proof != SIZE_MAX && pt_proof <= sc_proof) {            // on a tie the point is reported
+      if (first_bad) *first_bad = pt_proof;
+      snprintf(msg, sizeof msg, "proof %llu: point %s rejected: %s", (unsigned long long)pt_proof, VERIFY_POINT_NAME[pt_field],
+               pt_reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
+               : pt_reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
+                                              : "not in the prime-order subgroup");
+      return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+    }
+    const uint32_t field = (uint32_t)(scalar_bad & 15);
+    if (first_bad) *first_bad = sc_proof;
+    snprintf(msg, sizeof msg, "proof %llu: %s is not a canonical scalar (>= q)", (unsigned long long)sc_proof,
+             field < VERIFY_EVALS ? VERIFY_EVAL_NAME[field] : field == VERIFY_BAD_PUBLIC ? "a public input" : field == VERIFY_BAD_WEIGHT ? "the weight" : "a challenge");
+    return fail(ctx, BP_ERR_BAD_SCALAR, msg, hipSuccess, __FILE__, __LINE__);
+  }
+
+  // stage 4: B over all 9 m + 9 points, A over the slice [7 m, 9 m) of the same array
+  BP_TRY(srs_to28_into(ctx, d_pts, n_all, d_p28));
+  MsmPending pend_b, pend_a;
+  BP_TRY(msm_launch(ctx, d_p28, n_all, d_b, BP_FR_MONT, 0, 0, 0, nullptr, &pend_b));
+  int rc = msm_launch(ctx, d_p28 + 7 * m, 2 * m, d_a, BP_FR_MONT, 0, 0, 1, nullptr, &pend_a);
+  const bool a_launched = rc == BP_OK;
+  if (a_launched) {
+    hipError_t he = hipEventRecord(ev[5], st);
+    if (he != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "hipEventRecord", he, __FILE__, __LINE__);
+  }
+  g1_proj A = g1_identity(), B = g1_identity();
+  const int rb = msm_finish(ctx, pend_b, &B);                      // every launched MSM is waited for, also after an error
+  if (rc == BP_OK) rc = rb;
+  if (a_launched) {
+    const int ra = msm_finish(ctx, pend_a, &A);
+    if (rc == BP_OK) rc = ra;
+  }
+  BP_TRY(rc);
+  for (int k = 0; k < 5; k++) BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_ms[k], ev[k], ev[k + 1]));
+  host_encode96(out192, A);
+  host_encode96(out192 + 96, B);
+  return BP_OK;
+}
+
+int bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                     size_t n_public, const void* weights, const void* challenges, int scalar_fmt, uint8_t out192[192], size_t* first_bad) {
+  if (!ctx || !vk768 || !out192 || !fmt_ok(scalar_fmt) || (m && !proofs624) || (m && n_public && !public_inputs)) return BP_ERR_INVALID_ARG;
+  if (log_n < 3 || log_n > 28) return fail(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: log_n outside 3..28", hipSuccess, __FILE__, __LINE__);
+  if (!weights && m > 1) return fail(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: weights may be NULL for a single proof only", hipSuccess, __FILE__, __LINE__);
+  if (n_public > ((size_t)1 << log_n)) return fail(ctx, BP_ERR_LENGTH, "bp_verify_reduce: more public inputs than rows", hipSuccess, __FILE__, __LINE__);
+  if (m >= (((size_t)1 << 31) - VERIFY_SHARED + VERIFY_POINTS - 1) / VERIFY_POINTS)
+    return fail(ctx, BP_ERR_TOO_LARGE, "bp_verify_reduce: 9 m + 9 >= 2^31 points", hipSuccess, __FILE__, __LINE__);
+  if (first_bad) *first_bad = SIZE_MAX;
+  if (m == 0) {
+    encode_identity_pair(out192);
+    for (float& v : ctx->verify_ms) v = 0;
+    return BP_OK;
+  }
+  DeviceGuard guard(ctx->device);
+  for (float& v : ctx->verify_ms) v = 0;
+  return verify_reduce_run(ctx, log_n, vk768, proofs624, m, public_inputs, n_public, weights, challenges, scalar_fmt, out192, first_bad);
+}
+
+int bp_verify_last_stats(bp_ctx* ctx, float stage_ms[5]) {
+  if (!ctx || !stage_ms) return BP_ERR_INVALID_ARG;
+  for (int k = 0; k < 5; k++) stage_ms[k] = ctx->verify_ms[k];
+  return BP_OK;
+}

@@ -126,6 +126,8 @@ struct bp_ctx {
   // the commitments' latency-bound tails and the host's transcript steps leave idle.  side_ev: [0] inputs ready, [1] side work done.
   bp_ctx* side = nullptr;
   hipEvent_t side_ev[2] = {nullptr, nullptr};
+  hipEvent_t verify_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // bp_verify_reduce: the boundaries of its five stages
+  float verify_ms[5] = {0, 0, 0, 0, 0};              // upload, transcript, scalars, decode + subgroup check, MSMs of the last bp_verify_reduce
   hipEvent_t seam_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // bp_msm_g1_projective144: piece k uploaded and normalised (recorded on the side stream)
   hipStream_t stream = nullptr;
   bool own_stream = true;

@@ -397,6 +397,48 @@ int  bp_prove_last_stats(bp_ctx* ctx, float round_ms[5], float* total_ms);
  * challenge_bytes("challenge", 32) -- lets a binding check the host transcript without a GPU. */
 int  bp_transcript_test_vector(uint8_t out32[32]);
 
+/* ---- Verifier::verify (src/verifier.rs:80-209) for a batch, up to the two pairings ------------------------------ */
+/* Verifier::compute_challengs (verifier.rs:193-209) for m proofs in the 624-byte encoding of bp_prove; host-side, no GPU.
+ * out: m x 6 scalars in scalar_fmt, order beta gamma alpha zeta nu mu.  The transcript absorbs the 48 compressed bytes of every
+ * point and the 32 little-endian bytes of every evaluation as they stand in the record (transcript.rs:66-69, 83-85); points are not
+ * decoded here.  An evaluation >= q (Scalar::from_bytes, scalar.rs:264-288) is BP_ERR_BAD_SCALAR with the lowest such record in
+ * *first_bad (may be NULL; SIZE_MAX on success).  m == 0: BP_OK. */
+int  bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void* out, size_t* first_bad);
+/* Verifier::verify (verifier.rs:80-192) up to, and without, the two pairings, for m proofs of ONE circuit.
+ * out192 = A || B (96-byte affine each, the identity as 0x40 then zeros) with
+ *   A = sum_j rho_j (W_zeta_j + mu_j W_zeta_omega_j)
+ *   B = sum_j rho_j (zeta_j W_zeta_j + mu_j zeta_j omega W_zeta_omega_j + F_j - E_j)          (verifier.rs:187-191)
+ * The batch is valid iff pairing(A, x_2) == pairing(B, G2Affine::generator()) (up to the 2^-128 of the weights); the pairings stay
+ * with the host (bls12_381::pairing).  bp_verify_reduce does not decide validity.
+ *   log_n          group order n = 2^log_n, 3 <= log_n <= 28; omega = root_of_unity(n); k1 = 2, k2 = 3 (verifier.rs:76-77, 89).
+ *   vk768          the eight commitments in the order bp_circuit_commitments writes them (QL QR QM QO QC S1 S2 S3; verifier.rs:61-68),
+ *                  checked like bp_srs_load (canonical, flags, on the curve -> BP_ERR_BAD_POINT), not subgroup-checked: the verifier
+ *                  computed them itself.
+ *   proofs624      m records of bp_prove's output.  Each of the 9 points goes through the CHECKED decoder (G1Affine::from_compressed,
+ *                  g1.rs:326-331: encoding, curve, subgroup; the identity 0xc0 00.. is a valid point); each of the 6 evaluations must
+ *                  be < q.  BP_ERR_BAD_POINT / BP_ERR_BAD_SCALAR with *first_bad (may be NULL) = the lowest failing proof index -- a
+ *                  bad point wins over a bad scalar only if its proof index is lower or equal -- bp_last_error names proof, field and
+ *                  reason, out192 is left untouched.  On success *first_bad = SIZE_MAX.
+ *   public_inputs  m x n_public scalars in scalar_fmt, row j = the vector handed to verify() for proof j (verifier.rs:99-104: negated,
+ *                  zero-padded to n).  n_public may be 0 (the pointer is then ignored); n_public > n is BP_ERR_LENGTH.  PI(zeta) and
+ *                  L_1(zeta) (verifier.rs:91-104) equal what i_ntt + coeffs_evaluate return for EVERY zeta, also where zeta^n = 1 (the
+ *                  value is then [zeta == omega^i]); O(n_public) products and one inversion per proof.
+ *   weights        m scalars rho_j in scalar_fmt, drawn by the caller AFTER it has seen the proofs, 128 bits of entropy or more each
+ *                  (the reference draws its randomness with thread_rng on the host, prover.rs:108-110).  NULL means rho_j = 1 and is
+ *                  accepted for m <= 1 only (BP_ERR_INVALID_ARG otherwise); with m == 1 and NULL the outputs are exactly the two
+ *                  G1Affine arguments of verifier.rs:187-191.
+ *   challenges     NULL = derived on the device from the proof bytes (verifier.rs:193-209).  Otherwise m x 6 scalars in scalar_fmt,
+ *                  order as bp_plonk_challenges, used instead (a host with another transcript).
+ * Canonical-bytes public inputs, weights and challenges >= q are BP_ERR_BAD_SCALAR with the proof index in *first_bad.
+ * m == 0: BP_OK, A = B = identity.  9 m + 9 >= 2^31: BP_ERR_TOO_LARGE.  Null pointers, bad format, log_n out of range:
+ * BP_ERR_INVALID_ARG.  A bp_init_multi context runs the batch on its primary device.  Blocking; ordered on the context's stream. */
+int  bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m,
+                      const void* public_inputs, size_t n_public, const void* weights, const void* challenges,
+                      int scalar_fmt, uint8_t out192[192], size_t* first_bad);
+/* HIP-event milliseconds of the stages of the last bp_verify_reduce: upload, transcript, scalars, decode + subgroup check, MSMs
+ * (all 0 after an empty or a rejected batch). */
+int  bp_verify_last_stats(bp_ctx* ctx, float stage_ms[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,22 @@ void shard_range(size_t n, size_t r, size_t R, size_t* lo, size_t* hi);
 std::vector<bp_ctx*> shards_of(bp_ctx* ctx);
 int lift(bp_ctx* ctx, bp_ctx* member, int rc);
 int ctx_create(bp_ctx** out, int device_id);
-// capi_msm.hip
+// capi_srs.hip
 int srs_find(bp_ctx* ctx, uint64_t handle, bp::SrsEntry** out);
+// One shard of an SRS: the member that holds it, the member's entry and handle, and the part [lo, hi) of the range asked for
+// that lies on it, in global point indices (lo >= hi: none of it does).
+struct SrsShard {
+  bp_ctx* m;
+  bp::SrsEntry* e;
+  uint64_t handle;
+  size_t lo, hi;
+};
+// The shards of the SRS `srs_handle` names on ctx (the leader of a group, or a plain context: one shard), in ascending point
+// order, each with its part of points [first, first + n) cut to the SRS's length (default: every point).  A member's lookup error
+// is lifted to ctx.  srs_shards_checked refuses a range that does not lie inside the SRS instead of cutting it.
+int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, size_t first = 0, size_t n = SIZE_MAX);
+int srs_shards_checked(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, std::vector<SrsShard>* out);
+// does an MSM of n points against this entry go through its fixed-base tables?
+bool srs_tables_pay(const bp::SrsEntry& e, size_t n);
 // capi_ntt.hip
 bool host_root_of_unity(bp::fr_t& out, uint64_t group_order);

@@ -1,398 +1,18 @@
-// capi_msm.hip -- C ABI, part 2: the SRS (Setup.powers_of_x resident in HBM, fixed-base tables) and the G1 MSM entry points
-// (BucketMSM::bucket_msm, Setup::commit over one GPU or the shards of a group context, records for the one-process-per-GPU path).
+// capi_msm.hip -- C ABI, part 2b: the G1 MSM entry points (BucketMSM::bucket_msm, Setup::commit over one GPU or the shards of a
+// group context, commit lanes, records for the one-process-per-GPU path) and their stats.  The SRS they read lives in capi_srs.hip.
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
+#include <string>
 #include <vector>
 
 #include "ctx.hpp"
-#include "g1_check.hpp"
 
 #include "capi_common.hpp"
 
 using namespace bp;
-// ---------------------------------------------------------------------------------------------- SRS
-// takes ownership of d (freed on failure); the entry covers global points [first, first + n) of an SRS of n_global points
-static int srs_register(bp_ctx* ctx, g1_affine* d, size_t n, size_t first, size_t n_global, uint64_t* handle) {
-  SrsEntry e;
-  e.d_points = d;
-  e.n = n;
-  e.first = first;
-  e.n_global = n_global;
-  int rc = srs_to28_run(ctx, d, n, &e.d_points28);
-  if (rc == BP_OK && stream_wait(ctx->stream) != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "srs_to28", hipGetLastError(), __FILE__, __LINE__);
-  if (rc != BP_OK) {
-    (void)hipFree(d);
-    if (e.d_points28) (void)hipFree(e.d_points28);
-    return rc;
-  }
-  *handle = ctx->next_handle++;
-  ctx->srs[*handle] = e;
-  return BP_OK;
-}
-int srs_find(bp_ctx* ctx, uint64_t handle, SrsEntry** out) {
-  auto it = ctx->srs.find(handle);
-  if (it == ctx->srs.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown SRS handle", hipSuccess, __FILE__, __LINE__);
-  *out = &it->second;
-  return BP_OK;
-}
-// handle of the shard held by member r (the leader's entry lists them; a plain context has only its own)
-static uint64_t member_handle(const SrsEntry& lead, uint64_t own, size_t r) { return lead.member_handle.empty() ? own : lead.member_handle[r]; }
 
-static int srs_free_one(bp_ctx* ctx, uint64_t handle) {
-  SrsEntry* e;
-  BP_TRY(srs_find(ctx, handle, &e));
-  DeviceGuard guard(ctx->device);
-  BP_HIP(ctx, stream_wait(ctx->stream));
-  BP_HIP(ctx, hipFree(e->d_points));
-  BP_HIP(ctx, hipFree(e->d_points28));
-  if (e->d_table) BP_HIP(ctx, hipFree(e->d_table));
-  ctx->srs.erase(handle);
-  return BP_OK;
-}
-
-// bytes per host record of the SRS kinds that upload one (0, 1, 4)
-static size_t srs_record_bytes(int kind) { return kind == 0 ? 96 : kind == 1 ? 144 : 48; }
-// BP_ERR_BAD_POINT naming global point `index` and the reason of the status word (g1_check.hpp)
-static int srs_bad_point(bp_ctx* ctx, uint64_t index, uint32_t reason, size_t* first_bad) {
-  if (first_bad) *first_bad = (size_t)index;
-  char msg[160];
-  snprintf(msg, sizeof msg, "point %llu rejected: %s", (unsigned long long)index,
-           reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
-           : reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
-                                       : "not in the prime-order subgroup");
-  return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
-}
-
-// One shard of an SRS on one device.  kind 0: decode 96-byte encodings, 1: normalise 144-byte projective images,
-// 2: generate tau^i G, 3: generate (a + i d) G, 4: decode 48-byte compressed encodings (+ the subgroup test when checks has
-// BP_SRS_CHECK_SUBGROUP; a rejected point's global index goes to *first_bad).  src: this shard's slice of the host input (kinds 0, 1, 4).
-static int srs_make_one(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a, const fr_t& d, size_t first, size_t n, size_t n_global,
-                        uint64_t* handle, uint32_t checks = 0, size_t* first_bad = nullptr) {
-  DeviceGuard guard(ctx->device);
-  g1_affine* d_pts = nullptr;
-  BP_HIP(ctx, hipMalloc((void**)&d_pts, std::max<size_t>(n, 1) * sizeof(g1_affine)));
-  int rc = BP_OK;
-  if (kind == 0 || kind == 1 || kind == 4) {
-    const size_t rec = srs_record_bytes(kind);
-    uint8_t* d_bytes = nullptr;
-    rc = ws_get(ctx, "io.bytes", n * rec, (void**)&d_bytes);
-    if (rc == BP_OK && n) {
-      hipError_t e = hipMemcpyAsync(d_bytes, src, n * rec, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "SRS upload", e, __FILE__, __LINE__);
-    }
-    if (rc == BP_OK && kind == 4) {
-      uint64_t bad = ~0ull;
-      rc = srs_decode48_run(ctx, d_bytes, n, (checks & BP_SRS_CHECK_SUBGROUP) != 0, d_pts, &bad);
-      if (rc == BP_OK && bad != ~0ull) rc = srs_bad_point(ctx, first + (bad >> 2), (uint32_t)(bad & 3), first_bad);
-    } else if (rc == BP_OK) {
-      rc = kind == 0 ? srs_decode_run(ctx, d_bytes, n, d_pts) : srs_from_projective_run(ctx, (const g1_proj*)d_bytes, n, d_pts);
-    }
-  } else {
-    rc = srs_generate_run(ctx, a, d, kind == 2 ? 0 : 1, first, n, d_pts);
-  }
-  if (rc == BP_OK) {
-    hipError_t e = stream_wait(ctx->stream);
-    if (e != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "SRS build", e, __FILE__, __LINE__);
-  }
-  if (rc != BP_OK) {
-    (void)hipFree(d_pts);
-    return rc;
-  }
-  return srs_register(ctx, d_pts, n, first, n_global, handle);
-}
-
-// the whole SRS: one shard per member (contiguous point ranges), the leader's entry lists the members' handles.
-// Shards are built in ascending order and the first failing one ends the build, so *first_bad (kind 4) is the lowest global index.
-static int srs_make(bp_ctx* ctx, int kind, const uint8_t* src, const fr_t& a, const fr_t& d, size_t n, uint64_t* handle, uint32_t checks = 0,
-                    size_t* first_bad = nullptr) {
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const size_t rec = srs_record_bytes(kind);
-  std::vector<uint64_t> hs;
-  for (size_t r = 0; r < sh.size(); r++) {
-    size_t lo, hi;
-    shard_range(n, r, sh.size(), &lo, &hi);
-    uint64_t h = 0;
-    int rc = lift(ctx, sh[r], srs_make_one(sh[r], kind, src ? src + lo * rec : nullptr, a, d, lo, hi - lo, n, &h, checks, first_bad));
-    if (rc != BP_OK) {
-      for (size_t k = 0; k < hs.size(); k++) (void)srs_free_one(sh[k], hs[k]);
-      return rc;
-    }
-    hs.push_back(h);
-  }
-  if (sh.size() > 1) ctx->srs[hs[0]].member_handle = hs;
-  *handle = hs[0];
-  return BP_OK;
-}
-
-int bp_srs_load(bp_ctx* ctx, const uint8_t* points96, size_t n, uint64_t* srs_handle) {
-  if (!ctx || !srs_handle || (n && !points96)) return BP_ERR_INVALID_ARG;
-  return srs_make(ctx, 0, points96, Fr::zero(), Fr::zero(), n, srs_handle);
-}
-int bp_srs_load_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n, uint64_t* srs_handle) {
-  if (!ctx || !srs_handle || (n && !points144)) return BP_ERR_INVALID_ARG;
-  return srs_make(ctx, 1, points144, Fr::zero(), Fr::zero(), n, srs_handle);
-}
-int bp_srs_load_compressed48(bp_ctx* ctx, const uint8_t* points48, size_t n, uint32_t checks, uint64_t* srs_handle, size_t* first_bad) {
-  if (first_bad) *first_bad = SIZE_MAX;
-  if (!ctx || !srs_handle || (n && !points48) || (checks & ~BP_SRS_CHECK_SUBGROUP)) return BP_ERR_INVALID_ARG;
-  return srs_make(ctx, 4, points48, Fr::zero(), Fr::zero(), n, srs_handle, checks, first_bad);
-}
-
-static int srs_generate_common(bp_ctx* ctx, size_t n, const uint8_t a32[32], const uint8_t d32[32], int mode, uint64_t* handle) {
-  if (!ctx || !handle || !a32 || (mode == 1 && !d32)) return BP_ERR_INVALID_ARG;
-  fr_t a, d = Fr::zero();
-  if (!fr_bytes_to_mont(a, a32, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
-  if (mode == 1 && !fr_bytes_to_mont(d, d32, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
-  return srs_make(ctx, mode == 0 ? 2 : 3, nullptr, a, d, n, handle);
-}
-int bp_srs_generate(bp_ctx* ctx, size_t powers, const uint8_t tau32[32], uint64_t* srs_handle) {
-  return srs_generate_common(ctx, powers, tau32, nullptr, 0, srs_handle);
-}
-int bp_srs_generate_progression(bp_ctx* ctx, size_t n, const uint8_t a32[32], const uint8_t d32[32], uint64_t* srs_handle) {
-  return srs_generate_common(ctx, n, a32, d32, 1, srs_handle);
-}
-
-int bp_srs_len(bp_ctx* ctx, uint64_t srs_handle, size_t* n) {
-  if (!ctx || !n) return BP_ERR_INVALID_ARG;
-  SrsEntry* e;
-  BP_TRY(srs_find(ctx, srs_handle, &e));
-  *n = e->n_global;
-  return BP_OK;
-}
-
-// points [first, first + n) of every shard they lie on, encoded on the device: rec = 96 (to_uncompressed) or 48 (to_compressed)
-static int srs_export_bytes(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* out, size_t rec) {
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  if (first > lead->n_global || n > lead->n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  for (size_t r = 0; r < sh.size(); r++) {
-    bp_ctx* m = sh[r];
-    SrsEntry* e;
-    BP_TRY(lift(ctx, m, srs_find(m, member_handle(*lead, srs_handle, r), &e)));
-    const size_t lo = std::max(first, e->first), hi = std::min(first + n, e->first + e->n);
-    if (lo >= hi) continue;
-    DeviceGuard guard(m->device);
-    uint8_t* d_bytes;
-    BP_TRY(lift(ctx, m, ws_get(m, "io.bytes", (hi - lo) * rec, (void**)&d_bytes)));
-    const g1_affine* src = e->d_points + (lo - e->first);
-    BP_TRY(lift(ctx, m, rec == 96 ? srs_encode_run(m, src, hi - lo, d_bytes) : srs_encode48_run(m, src, hi - lo, d_bytes)));
-    BP_HIP(ctx, hipMemcpyAsync(out + (lo - first) * rec, d_bytes, (hi - lo) * rec, hipMemcpyDeviceToHost, m->stream));
-    BP_HIP(ctx, stream_wait(m->stream));
-  }
-  return BP_OK;
-}
-int bp_srs_export(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points96) {
-  if (!ctx || (n && !points96)) return BP_ERR_INVALID_ARG;
-  return srs_export_bytes(ctx, srs_handle, first, n, points96, 96);
-}
-int bp_srs_export_compressed48(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points48) {
-  if (!ctx || (n && !points48)) return BP_ERR_INVALID_ARG;
-  return srs_export_bytes(ctx, srs_handle, first, n, points48, 48);
-}
-
-int bp_srs_check_subgroup(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, size_t* first_bad) {
-  if (first_bad) *first_bad = SIZE_MAX;
-  if (!ctx) return BP_ERR_INVALID_ARG;
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  if (first > lead->n_global || n > lead->n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  for (size_t r = 0; r < sh.size(); r++) {            // shards in ascending point order: the first failing one holds the lowest index
-    bp_ctx* m = sh[r];
-    SrsEntry* e;
-    BP_TRY(lift(ctx, m, srs_find(m, member_handle(*lead, srs_handle, r), &e)));
-    const size_t lo = std::max(first, e->first), hi = std::min(first + n, e->first + e->n);
-    if (lo >= hi) continue;
-    DeviceGuard guard(m->device);
-    uint64_t bad = ~0ull;
-    BP_TRY(lift(ctx, m, srs_subgroup_run(m, e->d_points + (lo - e->first), hi - lo, &bad)));
-    if (bad != ~0ull) return srs_bad_point(ctx, lo + (bad >> 2), (uint32_t)(bad & 3), first_bad);
-  }
-  return BP_OK;
-}
-
-int bp_srs_export_projective144(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, uint8_t* points144) {
-  if (!ctx || (n && !points144)) return BP_ERR_INVALID_ARG;
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  if (first > lead->n_global || n > lead->n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const fp_t one = Fp::one();
-  for (size_t r = 0; r < sh.size(); r++) {
-    bp_ctx* m = sh[r];
-    SrsEntry* e;
-    BP_TRY(lift(ctx, m, srs_find(m, member_handle(*lead, srs_handle, r), &e)));
-    const size_t lo = std::max(first, e->first), hi = std::min(first + n, e->first + e->n);
-    if (lo >= hi) continue;
-    DeviceGuard guard(m->device);
-    std::vector<g1_affine> aff(hi - lo);
-    BP_HIP(ctx, hipMemcpyAsync(aff.data(), e->d_points + (lo - e->first), (hi - lo) * sizeof(g1_affine), hipMemcpyDeviceToHost, m->stream));
-    BP_HIP(ctx, stream_wait(m->stream));
-    for (size_t i = 0; i < hi - lo; i++) {                   // G1Projective::from(&G1Affine) (g1.rs:176-190): z = 1, or 0 for the identity
-      g1_proj p;
-      p.x = aff[i].x;
-      p.y = aff[i].y;
-      p.z = g1_affine_is_identity(aff[i]) ? Fp::zero() : one;
-      if (g1_affine_is_identity(aff[i])) p = g1_identity();
-      memcpy(points144 + (lo - first + i) * 144, &p, 144);
-    }
-  }
-  return BP_OK;
-}
-
-int bp_srs_free(bp_ctx* ctx, uint64_t srs_handle) {
-  if (!ctx) return BP_ERR_INVALID_ARG;
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const std::vector<uint64_t> hs = lead->member_handle;
-  int rc = BP_OK;
-  for (size_t r = sh.size(); r-- > 0;) {                 // the leader's entry (r = 0) goes last: it names the others
-    const int rc1 = lift(ctx, sh[r], srs_free_one(sh[r], hs.empty() ? srs_handle : hs[r]));
-    if (rc == BP_OK) rc = rc1;
-  }
-  return rc;
-}
-
-static int srs_precompute_one(bp_ctx* ctx, uint64_t handle, uint32_t c) {
-  SrsEntry* e;
-  BP_TRY(srs_find(ctx, handle, &e));
-  DeviceGuard guard(ctx->device);
-  BP_HIP(ctx, stream_wait(ctx->stream));
-  if (e->d_table) {
-    BP_HIP(ctx, hipFree(e->d_table));
-    e->d_table = nullptr;
-    e->table_c = e->table_W = 0;
-  }
-  if (c == BP_SRS_TABLES_OFF) return BP_OK;
-  BP_TRY(srs_tables_run(ctx, e->d_points, e->d_points28, e->n, c, &e->d_table, &e->table_W));
-  e->table_c = c;
-  return BP_OK;
-}
-
-int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
-  if (!ctx) return BP_ERR_INVALID_ARG;
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  uint32_t c = window_bits;
-  if (c == 0) {                       // auto, from the length of one shard (every shard of a group gets the same width)
-    uint32_t lg = 0;
-    const uint64_t n = lead->n;
-    while ((2ull << lg) <= n) lg++;                       // floor(log2 n)
-    if (lg >= 24) {                   // 12 windows: the 2^21-bucket tree (+0.8 ms) against n fewer additions (-1.8 ms at 2^24; a tie at 2^23)
-      c = 22;
-    } else if (lg >= 20) {            // 13 windows instead of 16: pays once the sort and the 2^19-bucket tree are small against
-      c = 20;                         // 3 x n additions (round 3: -3 % at 2^20, -6 % at 2^21, -12 % at 2^22; profiles/r03_window_width_ab.txt)
-    } else if (n >= (1u << 14)) {     // throughput regime: reduction work 2^c stays below the bucket-add work W * n
-      c = lg + 2 > 16 ? 16 : lg + 2;
-    } else {                          // latency regime (a few thousand points): every kernel is a dependent chain, and the
-      c = lg > 8 ? lg - 4 : 4;        // reduction tree has c - 1 levels -- measured optimum 2^10: 6, 2^12: 8
-    }
-  }
-  const bool naf = (c & MSM_NAF_FLAG) != 0;
-  if (naf && !EXPERIMENT_BUILD)        // every-position tables with NAF digits: measured slower twice, experiment builds only
-    return fail(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off) or 4..24", hipSuccess, __FILE__, __LINE__);
-  if (naf ? ((c & 0xffu) < 6 || (c & 0xffu) > 22 || (c >> 9)) : (c != BP_SRS_TABLES_OFF && (c < 4 || c > 24)))
-    return fail(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off), 4..24, or 256 + w (w = 6..22: every-position tables)", hipSuccess,
-                __FILE__, __LINE__);
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const std::vector<uint64_t> hs = lead->member_handle;
-  // Memory budget: the tables (rows x points x 128 B: 25.8 GB per GPU at 2^24 points) must fit beside whatever else lives on the
-  // device -- a second prover context, the caller's tensors -- together with the workspaces the first MSM against them allocates.
-  // The check comes BEFORE anything is released or allocated, and counts the bytes of the tables this SRS holds now as free (they
-  // go once the new width is accepted): a refused explicit width therefore leaves the SRS exactly as it was, old tables included.
-  // An automatic width that does not fit falls back to wider windows (fewer rows: 22 -> 12, 24 -> 11) -- but only to a width MSMs over
-  // this SRS would use (8 n >= 2^c, the rule of msm_shard_launch: a 2^18-point SRS never builds 24-bit tables no MSM would touch) --
-  // and then to NO tables (the MSM runs on the raw points, same bytes out: bp_srs_table_info reports what was built); an explicit
-  // width that does not fit is an error that says how much is missing, not an out-of-memory failure halfway through the build.
-  if (c == BP_SRS_TABLES_OFF) {
-    for (size_t r = 0; r < sh.size(); r++) BP_TRY(lift(ctx, sh[r], srs_precompute_one(sh[r], hs.empty() ? srs_handle : hs[r], BP_SRS_TABLES_OFF)));
-    return BP_OK;
-  }
-  auto fits = [&](uint32_t cc, size_t* need_out, size_t* free_out) -> int {
-    std::map<int, size_t> per_device, held;              // shards that share a device (a rehearsal group) share its free memory
-    for (size_t r = 0; r < sh.size(); r++) {
-      SrsEntry* e;
-      BP_TRY(lift(ctx, sh[r], srs_find(sh[r], hs.empty() ? srs_handle : hs[r], &e)));
-      DeviceGuard guard(sh[r]->device);
-      size_t free_b = 0, total_b = 0;
-      BP_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-      if (ctx->free_bytes_probe) free_b = (size_t)ctx->free_bytes_probe;        // tests: the reading to decide on (bpx_set_free_bytes_probe below)
-      const size_t rows = srs_table_rows(cc);
-      size_t& need = per_device[sh[r]->device];
-      size_t& old_bytes = held[sh[r]->device];
-      if (e->d_table) old_bytes += (size_t)e->table_W * std::max<size_t>(e->n, 1) * sizeof(g1_affine28);
-      need += rows * e->n * (sizeof(g1_affine28) + 24) + ((size_t)256 << 20);      // + sort records, lists, partial slots of one MSM
-      if (need > free_b + old_bytes) {
-        *need_out = need;
-        *free_out = free_b + old_bytes;
-        return 1;
-      }
-    }
-    return 0;
-  };
-  size_t need = 0, free_b = 0;
-  int rc = fits(c, &need, &free_b);
-  if (rc < 0) return rc;
-  if (rc == 1) {
-    if (window_bits != 0) {
-      char msg[200];
-      snprintf(msg, sizeof msg, "fixed-base tables of width %u need %.1f GiB on a device with %.1f GiB free", c & 0xffu, need / 1073741824.0, free_b / 1073741824.0);
-      return fail(ctx, BP_ERR_TOO_LARGE, msg, hipSuccess, __FILE__, __LINE__);
-    }
-    uint32_t pick = BP_SRS_TABLES_OFF;
-    for (uint32_t cc : {22u, 24u}) {
-      if (cc <= c || 8 * (uint64_t)lead->n < (1ull << cc)) continue;
-      rc = fits(cc, &need, &free_b);
-      if (rc < 0) return rc;
-      if (rc == 0) { pick = cc; break; }
-    }
-    c = pick;
-  }
-  // accepted (or nothing fits: the SRS ends up without tables): only now do the old tables go
-  for (size_t r = 0; r < sh.size(); r++) BP_TRY(lift(ctx, sh[r], srs_precompute_one(sh[r], hs.empty() ? srs_handle : hs[r], BP_SRS_TABLES_OFF)));
-  if (c == BP_SRS_TABLES_OFF) return BP_OK;
-  for (size_t r = 0; r < sh.size(); r++) BP_TRY(lift(ctx, sh[r], srs_precompute_one(sh[r], hs.empty() ? srs_handle : hs[r], c)));
-  return BP_OK;
-}
-
-// INTERNAL, not part of include/bp_msm_ntt.h: the memory-budget decision of bp_srs_precompute made testable without filling a
-// 288-GB device (a test that hogs memory until ~400 MiB are left depends on when other processes' frees reach the
-// driver).  bytes != 0: bp_srs_precompute on this context decides as if hipMemGetInfo had reported that many free bytes on every
-// device (the bytes of the tables the SRS holds now still count as free on top); 0: the real reading again.  Nothing else reads it.
-extern "C" int bpx_set_free_bytes_probe(bp_ctx* ctx, uint64_t bytes) {
-  if (!ctx) return BP_ERR_INVALID_ARG;
-  ctx->free_bytes_probe = bytes;
-  return BP_OK;
-}
-
-int bp_srs_table_info(bp_ctx* ctx, uint64_t srs_handle, uint32_t* window_bits, uint32_t* windows, uint64_t* bytes) {
-  if (!ctx) return BP_ERR_INVALID_ARG;
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  if (window_bits) *window_bits = lead->table_c;
-  if (windows) *windows = lead->table_W;
-  if (bytes) {
-    *bytes = 0;
-    const std::vector<bp_ctx*> sh = shards_of(ctx);
-    for (size_t r = 0; r < sh.size(); r++) {
-      SrsEntry* e;
-      BP_TRY(lift(ctx, sh[r], srs_find(sh[r], member_handle(*lead, srs_handle, r), &e)));
-      if (e->d_table) *bytes += (uint64_t)e->table_W * e->n * sizeof(g1_affine28);
-    }
-  }
-  return BP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- MSM
 // Enqueue the MSM of one shard: scalars[0..n) against the member's points [local_first, local_first + n).
 //   where 0: `scalars` is host memory; 1: HBM of this member's device; 2: HBM of device src_device (the leader's): copied
 //   GPU to GPU into the member's workspace once the leader's stream has reached `ready`.
@@ -413,9 +33,7 @@ static int msm_shard_launch(bp_ctx* m, SrsEntry* e, size_t local_first, const vo
     }
     d_scalars = d;
   }
-  // fixed-base tables pay once the bucket adds outweigh the fixed 2^table_c reduction
-  const bool tables = e->d_table && 8 * (uint64_t)n >= (1ull << ((e->table_c & MSM_NAF_FLAG) ? (e->table_c & 0xffu) - 2 : e->table_c));
-  if (tables) return msm_launch(m, e->d_table + local_first, n, d_scalars, fmt, e->table_c, e->n, slot, d_blob, pend);
+  if (srs_tables_pay(*e, n)) return msm_launch(m, e->d_table + local_first, n, d_scalars, fmt, e->table_c, e->n, slot, d_blob, pend);
   return msm_launch(m, e->d_points28 + local_first, n, d_scalars, fmt, 0, 0, slot, d_blob, pend);
 }
 
@@ -428,12 +46,9 @@ struct ShardedPending {
 };
 static int msm_all_shards_launch(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
                                  int scalars_on_device, int slot, ShardedPending* sp) {
-  SrsEntry* lead;
-  BP_TRY(srs_find(ctx, srs_handle, &lead));
-  if (first > lead->n_global) return fail(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds", hipSuccess, __FILE__, __LINE__);
-  const size_t n = std::min(n_scalars, lead->n_global - first);          // zip() truncation, msm.rs:29
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const std::vector<uint64_t> hs = lead->member_handle;
+  std::vector<SrsShard> sh;
+  BP_TRY(srs_shards(ctx, srs_handle, &sh, first, n_scalars));            // more scalars than points: cut to the SRS (zip() truncation, msm.rs:29)
+  if (first > sh[0].e->n_global) return fail(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds", hipSuccess, __FILE__, __LINE__);
   if (sh.size() > 1 && scalars_on_device) {            // the members' copies must see what the leader's stream has produced
     DeviceGuard guard(ctx->device);
     BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
@@ -441,25 +56,19 @@ static int msm_all_shards_launch(bp_ctx* ctx, uint64_t srs_handle, size_t first,
   sp->pend.assign(sh.size(), MsmPending());
   sp->used.assign(sh.size(), false);
   sp->host_scalars = !scalars_on_device;
-  // every shard's range, then the launches: scalars already in HBM are enqueued by this thread (asynchronous copies and kernels);
+  // the launches: scalars already in HBM are enqueued by this thread (asynchronous copies and kernels);
   // host scalars go through the members' own threads, so that the uploads -- staged by the issuing thread when the memory is
   // pageable, as a Rust Vec<Scalar> is -- run on all PCIe links at once instead of one after another
-  struct Part { SrsEntry* e; size_t local_first, cnt; const uint8_t* sc; };
-  std::vector<Part> part(sh.size(), Part{nullptr, 0, 0, nullptr});
   std::vector<int> rcs(sh.size(), BP_OK);
   std::vector<bool> take(sh.size(), false);
-  for (size_t r = 0; r < sh.size(); r++) {
-    SrsEntry* e;
-    BP_TRY(lift(ctx, sh[r], srs_find(sh[r], hs.empty() ? srs_handle : hs[r], &e)));
-    const size_t lo = std::max(first, e->first), hi = std::min(first + n, e->first + e->n);
-    if (lo >= hi && !(sh.size() == 1)) continue;
-    part[r] = Part{e, lo < hi ? lo - e->first : 0, lo < hi ? hi - lo : 0, (const uint8_t*)scalars + (lo < hi ? (lo - first) * sizeof(fr_t) : 0)};
-    take[r] = true;
-  }
+  // a shard none of the range lies on is skipped -- except the only shard of a plain context: the empty MSM resets the stats and yields the identity
+  for (size_t r = 0; r < sh.size(); r++) take[r] = sh[r].lo < sh[r].hi || sh.size() == 1;
   auto launch_one = [&](size_t r) {
+    const SrsShard& s = sh[r];
+    const bool any = s.lo < s.hi;
     const int where = !scalars_on_device ? 0 : (r == 0 ? 1 : 2);
-    rcs[r] = msm_shard_launch(sh[r], part[r].e, part[r].local_first, part[r].sc, part[r].cnt, scalar_fmt, where, ctx->device, ctx->ev[4], slot, nullptr,
-                              &sp->pend[r]);
+    rcs[r] = msm_shard_launch(s.m, s.e, any ? s.lo - s.e->first : 0, (const uint8_t*)scalars + (any ? (s.lo - first) * sizeof(fr_t) : 0), any ? s.hi - s.lo : 0,
+                              scalar_fmt, where, ctx->device, ctx->ev[4], slot, nullptr, &sp->pend[r]);
   };
   if (!scalars_on_device && sh.size() > 1) {
     over_members(ctx, sh.size(), [&](size_t r) { return (bool)take[r]; }, launch_one);
@@ -471,7 +80,7 @@ static int msm_all_shards_launch(bp_ctx* ctx, uint64_t srs_handle, size_t first,
   for (size_t r = 0; r < sh.size(); r++) {
     if (!take[r]) continue;
     sp->used[r] = rcs[r] == BP_OK;             // a shard that failed to launch has nothing to wait for
-    const int rc1 = lift(ctx, sh[r], rcs[r]);
+    const int rc1 = lift(ctx, sh[r].m, rcs[r]);
     if (rc == BP_OK) rc = rc1;
   }
   return rc;               // the caller still finishes whatever was launched
@@ -538,18 +147,12 @@ constexpr int MSM_BATCH_MAX = 4;          // = MSM_MAX_BATCH of msm_kernels.hpp 
 // vectors every member receives its slice of each (peer copies behind the leader's event), runs ONE pipeline over the slices'
 // bucket sets and delivers one partial sum per vector; the host adds the members' partial sums.  BP_ERR_TOO_LARGE before anything
 // was launched = a member's batch does not fit one pipeline.
-static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, SrsEntry* lead, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out) {
-  const std::vector<bp_ctx*> sh = ctx->members;
-  const std::vector<uint64_t> hs = lead->member_handle;
-  const size_t R = sh.size();
-  std::vector<SrsEntry*> ent(R, nullptr);
-  for (size_t r = 0; r < R; r++) {
-    uint64_t h = hs.empty() ? srs_handle : hs[r];
-    auto it = sh[r]->srs.find(h);
-    if (it == sh[r]->srs.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown SRS handle", hipSuccess, __FILE__, __LINE__);
-    ent[r] = &it->second;
-    if (!ent[r]->d_table) return BP_ERR_TOO_LARGE;
-  }
+static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out) {
+  std::vector<SrsShard> sh;
+  BP_TRY(srs_shards(ctx, srs_handle, &sh));
+  const size_t R = sh.size(), n_global = sh[0].e->n_global;
+  for (const SrsShard& s : sh)
+    if (!s.e->d_table) return BP_ERR_TOO_LARGE;
   for (int base = 0; base < k; base += MSM_BATCH_MAX) {
     const int cnt = std::min(MSM_BATCH_MAX, k - base);
     {
@@ -561,13 +164,13 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, SrsEntry*
     std::vector<bool> used(R, false);
     int rc = BP_OK;
     for (size_t r = 0; r < R && rc == BP_OK; r++) {
-      bp_ctx* m = sh[r];
-      SrsEntry* e = ent[r];
+      bp_ctx* m = sh[r].m;
+      const SrsEntry* e = sh[r].e;
       DeviceGuard guard(m->device);
       const fr_t* ptrs[MSM_BATCH_MAX];
       size_t lens[MSM_BATCH_MAX], total = 0;
       for (int j = 0; j < cnt; j++) {
-        const size_t nj = std::min(n[base + j], lead->n_global);        // zip() truncation, msm.rs:29
+        const size_t nj = std::min(n[base + j], n_global);              // zip() truncation, msm.rs:29
         lens[j] = nj > e->first ? std::min(nj - e->first, e->n) : 0;
         total += lens[j];
       }
@@ -599,11 +202,11 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, SrsEntry*
     }
     std::vector<g1_proj> part(R * MSM_BATCH_MAX);
     over_members(ctx, R, [&](size_t r) { return (bool)used[r]; }, [&](size_t r) {
-      DeviceGuard guard(sh[r]->device);
-      rcs[r] = msm_finish(sh[r], pend[r], &part[r * MSM_BATCH_MAX]);
+      DeviceGuard guard(sh[r].m->device);
+      rcs[r] = msm_finish(sh[r].m, pend[r], &part[r * MSM_BATCH_MAX]);
     });
     for (size_t r = 0; r < R; r++)
-      if (used[r] && rc == BP_OK) rc = lift(ctx, sh[r], rcs[r]);
+      if (used[r] && rc == BP_OK) rc = lift(ctx, sh[r].m, rcs[r]);
     if (rc != BP_OK) return rc;
     for (int j = 0; j < cnt; j++) {
       g1_proj acc = g1_identity();
@@ -615,6 +218,20 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, SrsEntry*
   return BP_OK;
 }
 
+// lane j of a single-device context: 0 is the context itself, j >= 1 a context of its own on the same device (own stream and
+// workspaces).  lane_get creates the lanes up to j that do not exist yet.
+static bp_ctx* lane_of(bp_ctx* ctx, int j) { return j == 0 ? ctx : ctx->lanes[j - 1]; }
+static int lane_get(bp_ctx* ctx, int j, bp_ctx** out) {
+  while ((int)ctx->lanes.size() < j) {
+    bp_ctx* lane = nullptr;
+    int rc = ctx_create(&lane, ctx->device);
+    if (rc != BP_OK) return fail(ctx, rc, "commit lane", hipSuccess, __FILE__, __LINE__);
+    ctx->lanes.push_back(lane);
+  }
+  *out = lane_of(ctx, j);
+  return BP_OK;
+}
+
 int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out) {
   if (k <= 0) return BP_OK;
   SrsEntry* e;
@@ -622,7 +239,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
   if (is_group(ctx) && k > 1 && e->d_table) {   // group: ONE pipeline per member over its slices of up to MSM_BATCH_MAX commitments
     const char* v = knob("BP_COMMIT_BATCH");
     if (!(v && *v == '0')) {
-      int rc = commit_many_group_batched(ctx, srs_handle, e, d_coeffs, n, k, out);
+      int rc = commit_many_group_batched(ctx, srs_handle, d_coeffs, n, k, out);
       if (rc != BP_ERR_TOO_LARGE) return rc;       // too long for one pipeline somewhere: queue the commitments one by one below
     }
   }
@@ -653,8 +270,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
     const char* v = knob("BP_COMMIT_BATCH");
     size_t n_max = 0;
     for (int j = 0; j < k; j++) n_max = std::max(n_max, std::min(n[j], e->n));
-    const bool tables = e->d_table && 8 * (uint64_t)n_max >= (1ull << ((e->table_c & MSM_NAF_FLAG) ? (e->table_c & 0xffu) - 2 : e->table_c));
-    if (tables && v && *v == '1') {
+    if (srs_tables_pay(*e, n_max) && v && *v == '1') {
       bool ok = true;
       for (int base = 0; base < k && ok; base += (int)MSM_BATCH_MAX) {
         const int cnt = std::min((int)MSM_BATCH_MAX, k - base);
@@ -676,12 +292,8 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
       if (ok) return BP_OK;
     }
   }
-  while ((int)ctx->lanes.size() < MAX_LANES - 1 && (int)ctx->lanes.size() < k - 1) {
-    bp_ctx* lane = nullptr;
-    int rc = ctx_create(&lane, ctx->device);
-    if (rc != BP_OK) return fail(ctx, rc, "commit lane", hipSuccess, __FILE__, __LINE__);
-    ctx->lanes.push_back(lane);
-  }
+  bp_ctx* last;
+  BP_TRY(lane_get(ctx, std::min(MAX_LANES, k) - 1, &last));          // every lane the rounds below use exists before the first launch
   for (int base = 0; base < k; base += MAX_LANES) {
     const int cnt = std::min(MAX_LANES, k - base);
     BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on ctx->stream
@@ -689,7 +301,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
     bool used[MAX_LANES] = {false, false, false};
     int rc = BP_OK;
     for (int j = 0; j < cnt && rc == BP_OK; j++) {
-      bp_ctx* lane = j == 0 ? ctx : ctx->lanes[j - 1];
+      bp_ctx* lane = lane_of(ctx, j);
       if (lane != ctx) {
         hipError_t he = hipStreamWaitEvent(lane->stream, ctx->ev[4], 0);
         if (he != hipSuccess) { rc = fail(ctx, BP_ERR_HIP, "commit lane wait", he, __FILE__, __LINE__); break; }
@@ -700,7 +312,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
     }
     for (int j = 0; j < cnt; j++) {                                 // every launched lane is waited for, also after a failure elsewhere
       if (!used[j]) continue;
-      bp_ctx* lane = j == 0 ? ctx : ctx->lanes[j - 1];
+      bp_ctx* lane = lane_of(ctx, j);
       const int rc1 = lift(ctx, lane, msm_finish(lane, pend[j], &out[base + j]));
       if (rc == BP_OK) rc = rc1;
       if (lane != ctx && rc1 == BP_OK && lane->msm_accumulate_ms > ctx->msm_accumulate_ms) ctx->msm_accumulate_ms = lane->msm_accumulate_ms;
@@ -716,18 +328,13 @@ int commit_lane_launch(bp_ctx* ctx, int j, uint64_t srs_handle, const fr_t* d_co
   SrsEntry* e;
   BP_TRY(srs_find(ctx, srs_handle, &e));
   DeviceGuard guard(ctx->device);
-  while ((int)ctx->lanes.size() < j) {
-    bp_ctx* lane = nullptr;
-    int rc = ctx_create(&lane, ctx->device);
-    if (rc != BP_OK) return fail(ctx, rc, "commit lane", hipSuccess, __FILE__, __LINE__);
-    ctx->lanes.push_back(lane);
-  }
-  bp_ctx* lane = j == 0 ? ctx : ctx->lanes[j - 1];
+  bp_ctx* lane;
+  BP_TRY(lane_get(ctx, j, &lane));
   BP_HIP(ctx, hipStreamWaitEvent(lane->stream, ready, 0));
   return lift(ctx, lane, msm_shard_launch(lane, e, 0, d_coeffs, std::min(n, e->n), BP_FR_MONT, 1, ctx->device, nullptr, 0, nullptr, pend));     // zip() truncation, msm.rs:29
 }
 int commit_lane_finish(bp_ctx* ctx, int j, const MsmPending& pend, g1_proj* out) {
-  bp_ctx* lane = j == 0 ? ctx : ctx->lanes[j - 1];
+  bp_ctx* lane = lane_of(ctx, j);
   return lift(ctx, lane, msm_finish(lane, pend, out));
 }
 }  // namespace bp
@@ -840,8 +447,9 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
   return BP_OK;
 }
 
-int bp_msm_g1_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
-                          int scalars_on_device, void* d_blob) {
+// one MSM of a plain context against its SRS whose result stays in HBM as a record; wait: finish it (status, stats) before returning
+static int msm_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
+                           int scalars_on_device, void* d_blob, bool wait) {
   if (!ctx || !d_blob || !fmt_ok(scalar_fmt) || (n_scalars && !scalars)) return BP_ERR_INVALID_ARG;
   if (is_group(ctx)) return fail(ctx, BP_ERR_INVALID_ARG, "blob records are the one-process-per-GPU exchange; a bp_init_multi context combines its shards itself", hipSuccess, __FILE__, __LINE__);
   SrsEntry* e;
@@ -851,20 +459,7 @@ int bp_msm_g1_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const 
   DeviceGuard guard(ctx->device);
   MsmPending pend;
   BP_TRY(msm_shard_launch(ctx, e, first, scalars, n, scalar_fmt, scalars_on_device ? 1 : 0, ctx->device, nullptr, 0, d_blob, &pend));
-  return msm_finish(ctx, pend, nullptr);
-}
-
-int bp_msm_g1_blob_device_async(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
-                                int scalars_on_device, void* d_blob) {
-  if (!ctx || !d_blob || !fmt_ok(scalar_fmt) || (n_scalars && !scalars)) return BP_ERR_INVALID_ARG;
-  if (is_group(ctx)) return fail(ctx, BP_ERR_INVALID_ARG, "blob records are the one-process-per-GPU exchange; a bp_init_multi context combines its shards itself", hipSuccess, __FILE__, __LINE__);
-  SrsEntry* e;
-  BP_TRY(srs_find(ctx, srs_handle, &e));
-  if (first > e->n) return fail(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds", hipSuccess, __FILE__, __LINE__);
-  const size_t n = std::min(n_scalars, e->n - first);
-  DeviceGuard guard(ctx->device);
-  MsmPending pend;
-  BP_TRY(msm_shard_launch(ctx, e, first, scalars, n, scalar_fmt, scalars_on_device ? 1 : 0, ctx->device, nullptr, 0, d_blob, &pend));
+  if (wait) return msm_finish(ctx, pend, nullptr);
   // nothing is waited for: the stats of this MSM are read from its events by bp_msm_last_stats once the stream has passed them
   ctx->msm_async_pending = !pend.empty;
   ctx->msm_c = pend.tables == 2 ? (MSM_NAF_FLAG | (pend.c + 1)) : pend.c;
@@ -872,6 +467,14 @@ int bp_msm_g1_blob_device_async(bp_ctx* ctx, uint64_t srs_handle, size_t first, 
   ctx->msm_adds = pend.adds;
   if (pend.empty) ctx->msm_accumulate_ms = ctx->msm_total_ms = 0;
   return BP_OK;
+}
+int bp_msm_g1_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
+                          int scalars_on_device, void* d_blob) {
+  return msm_blob_device(ctx, srs_handle, first, scalars, n_scalars, scalar_fmt, scalars_on_device, d_blob, true);
+}
+int bp_msm_g1_blob_device_async(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
+                                int scalars_on_device, void* d_blob) {
+  return msm_blob_device(ctx, srs_handle, first, scalars, n_scalars, scalar_fmt, scalars_on_device, d_blob, false);
 }
 
 int bp_msm_blobs_sum_device(bp_ctx* ctx, const void* d_blobs, size_t n_blobs, void* d_out_blob) {

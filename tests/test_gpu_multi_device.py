@@ -458,3 +458,48 @@ def test_commit_many_device():
     t2 = time.perf_counter()
     print("three 2^20 commitments: one at a time %.2f ms, together %.2f ms" % (1e3 * (t1 - t0) / 3, 1e3 * (t2 - t1) / 3))
     ctx.close()
+
+
+def test_srs_ranges_across_shard_seams():
+    """every entry point that walks an SRS range over the shards of a group, on ranges that start and end on and around the seams:
+    exports in the three encodings are the single-device bytes (and the fixture's), the subgroup check passes shard by shard, the
+    tables cover every point once, and a range past the end is refused by each"""
+    raw = open(os.path.join(ROOT, "tests", "golden", "g1_uncompressed_valid_test_vectors.dat"), "rb").read()
+    raw48 = open(os.path.join(ROOT, "tests", "golden", "g1_compressed_valid_test_vectors.dat"), "rb").read()
+    one, many = bp.Context(0), bp.Context([0, 0, 0])
+    h1, hm = one.srs_load(raw), many.srs_load(raw)
+    n, R = many.srs_len(hm), many.n_shards()
+    assert n == 1000 and one.srs_len(h1) == n and R == 3
+    # the group's split: contiguous ranges, the first n % R shards one point longer
+    seams = [r * (n // R) + min(r, n % R) for r in range(1, R)]
+    ranges = [(0, 0), (0, 1), (333, 1), (332, 3), (100, 777), (999, 1), (1000, 0), (0, 1000)]
+    for s in seams:                                   # ... and whatever the split is: up to, from and across each seam
+        ranges += [(s - 1, 1), (s, 1), (s - 1, 2), (s, 0)]
+    assert all(any(f + c == s for f, c in ranges) and any(f == s for f, c in ranges) and any(f < s < f + c for f, c in ranges) for s in seams)
+    image = one.srs_export_projective144(h1)
+    z = image.reshape(n, 144)[:, 96:]
+    identity = np.array([bool(raw[96 * i] & 0x40) for i in range(n)])
+    assert identity.any() and not z[identity].any() and z[~identity].any(axis=1).all() and (z[~identity] == z[~identity][0]).all()
+    h2 = one.srs_load_projective144(image)            # G1Projective::from(&G1Affine) and back: the image names the fixture's points
+    assert one.srs_export(h2) == raw
+    for first, cnt in ranges:
+        where = (first, cnt)
+        assert one.srs_export(h1, first, cnt) == raw[96 * first: 96 * (first + cnt)], where
+        assert many.srs_export(hm, first, cnt) == one.srs_export(h1, first, cnt), where
+        assert one.srs_export_compressed48(h1, first, cnt) == raw48[48 * first: 48 * (first + cnt)], where
+        assert many.srs_export_compressed48(hm, first, cnt) == one.srs_export_compressed48(h1, first, cnt), where
+        assert one.srs_export_projective144(h1, first, cnt).tobytes() == image[144 * first: 144 * (first + cnt)].tobytes(), where
+        assert many.srs_export_projective144(hm, first, cnt).tobytes() == one.srs_export_projective144(h1, first, cnt).tobytes(), where
+        assert many.srs_check_subgroup(hm, first, cnt) is None, where
+    for ctx, h in ((one, h1), (many, hm)):
+        info = ctx.srs_precompute(h, 6)
+        assert info["window_bits"] == 6 and info["windows"] > 0 and info["bytes"] == info["windows"] * 1000 * 128
+        assert ctx.srs_table_info(h) == info
+    for first, cnt in ((1000, 1), (1001, 0)):
+        for ctx, h in ((one, h1), (many, hm)):
+            for call in (ctx.srs_export, ctx.srs_export_compressed48, ctx.srs_export_projective144, ctx.srs_check_subgroup):
+                with pytest.raises(bp.BpError) as e:
+                    call(h, first, cnt)
+                assert e.value.code == -1 and "SRS range out of bounds" in str(e.value), (call.__name__, first, cnt)
+    many.close()
+    one.close()

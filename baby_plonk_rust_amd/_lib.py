@@ -134,6 +134,7 @@ SIGNATURES = {
     "bp_poly_div_device": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _pp(_sz)]),
     "bp_poly_evaluate_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
     "bp_poly_scale_powers_device": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "bp_poly_last_stats": (_int, [_vp, _pp(_u32), _pp(_u64), _pp(_u32)]),
     "bp_roots_of_unity_device": (_int, [_vp, _u64, _vp]),
     "bp_grand_product_device": (_int, [_vp] + [_vp] * 6 + [_sz] + [_vp] * 4 + [_vp]),
     "bp_commit_device": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),

@@ -338,6 +338,13 @@ class Context:
         self.check(self._lib.bp_ntt_last_stats(self._h, C.byref(ms), C.byref(p)), "bp_ntt_last_stats")
         return {"device_ms": ms.value, "passes": p.value, "members": self._lib.bp_ntt_last_members(self._h)}
 
+    def poly_stats(self):
+        """which path the last polynomial division took (bp_poly_last_stats): div_path 0 general, 1 binomial in one chunk, 2 plain
+        carry, 3 workgroup carry, 4 segmented; chunks per chain; segments per chain (0 unless segmented)"""
+        p, ch, g = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        self.check(self._lib.bp_poly_last_stats(self._h, C.byref(p), C.byref(ch), C.byref(g)), "bp_poly_last_stats")
+        return {"div_path": p.value, "chunks": ch.value, "segments": g.value}
+
     def synthetic_scalars_device(self, ptr, n, seed):
         """fill HBM at `ptr` with n synthetic Montgomery scalars (the same stream the CPU baseline uses)"""
         self.check(self._lib.bp_fr_synthetic_device(self._h, ptr, n, seed), "bp_fr_synthetic_device")

@@ -10,8 +10,10 @@ inline bool basis_ok(int b) { return b == BP_BASIS_LAGRANGE || b == BP_BASIS_MON
 // capi_ctx.hip
 bool fr_bytes_to_mont(bp::fr_t& out, const uint8_t* b32, int fmt);
 void fr_mont_to_bytes(uint8_t* b32, const bp::fr_t& v, int fmt);
-int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, bp::fr_t** out);
-int download_fr(bp_ctx* ctx, bp::fr_t* d, void* host, size_t n, int fmt);
+// d_bad (bp::fr_bad_word): upload_fr raises it for a canonical-bytes input >= q; download_fr reads it with the copy that ends the
+// call and returns BP_ERR_BAD_SCALAR when it is set (`host` is then unspecified)
+int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, bp::fr_t** out, uint32_t* d_bad = nullptr);
+int download_fr(bp_ctx* ctx, bp::fr_t* d, void* host, size_t n, int fmt, const uint32_t* d_bad = nullptr);
 // work(r) for every member r for which use(r) holds: member 0 on the calling thread, the others on their own threads, all at once
 void over_members(bp_ctx* ctx, size_t R, const std::function<bool(size_t)>& use, const std::function<void(size_t)>& work);
 void shard_range(size_t n, size_t r, size_t R, size_t* lo, size_t* hi);

@@ -199,19 +199,22 @@ void fr_mont_to_bytes(uint8_t* b32, const fr_t& v, int fmt) {
 }
 
 // upload n scalars to workspace `name`, converting to Montgomery form on the device if needed
-int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, fr_t** out) {
+int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, fr_t** out, uint32_t* d_bad) {
   fr_t* d;
   BP_TRY(ws_get(ctx, name, std::max(cap_elems, n) * sizeof(fr_t), (void**)&d));
   if (n) BP_HIP(ctx, hipMemcpyAsync(d, host, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-  if (fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, n, 0));
+  if (fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, n, 0, d_bad));
   *out = d;
   return BP_OK;
 }
-int download_fr(bp_ctx* ctx, fr_t* d, void* host, size_t n, int fmt) {
-  if (n == 0) return BP_OK;
-  if (fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, n, 1));
-  BP_HIP(ctx, hipMemcpyAsync(host, d, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+int download_fr(bp_ctx* ctx, fr_t* d, void* host, size_t n, int fmt, const uint32_t* d_bad) {
+  if (n == 0 && !d_bad) return BP_OK;
+  uint32_t bad = 0;
+  if (n && fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, n, 1));
+  if (n) BP_HIP(ctx, hipMemcpyAsync(host, d, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
+  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);
   return BP_OK;
 }
 

@@ -189,9 +189,16 @@ int bp_ntt_fr(bp_ctx* ctx, void* data, uint32_t log_n, int inverse, int scalar_f
   ctx->ntt_members = 1;
   const size_t span = (batch - 1) * stride + N;
   fr_t* d;
-  BP_TRY(upload_fr(ctx, "io.ntt", data, span, span, scalar_fmt, &d));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  if (bad && batch > 1 && stride > N) {      // what lies between the vectors is not input: converted as before, not judged
+    BP_TRY(upload_fr(ctx, "io.ntt", data, span, span, BP_FR_MONT, &d));
+    BP_TRY(fr_flag_noncanonical_run(ctx, d, batch * N, bad, N, stride));
+    BP_TRY(fr_convert_run(ctx, d, span, 0));
+  } else
+    BP_TRY(upload_fr(ctx, "io.ntt", data, span, span, scalar_fmt, &d, bad));
   BP_TRY(ntt_run(ctx, d, log_n, inverse, batch, stride));
-  BP_TRY(download_fr(ctx, d, data, span, scalar_fmt));
+  BP_TRY(download_fr(ctx, d, data, span, scalar_fmt, bad));
   BP_HIP(ctx, hipEventElapsedTime(&ctx->ntt_ms, ctx->ev[0], ctx->ev[1]));
   return BP_OK;
 }

@@ -24,8 +24,10 @@ int bp_poly_evaluate(bp_ctx* ctx, const void* coeffs, size_t n, int basis, const
   if (!fr_bytes_to_mont(x, (const uint8_t*)x32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   DeviceGuard guard(ctx->device);
   fr_t* d;
-  BP_TRY(upload_fr(ctx, "io.poly_a", coeffs, n, n, scalar_fmt, &d));
-  BP_TRY(poly_eval_run(ctx, d, n, x, &r));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  BP_TRY(upload_fr(ctx, "io.poly_a", coeffs, n, n, scalar_fmt, &d, bad));
+  BP_TRY(poly_eval_run(ctx, d, n, x, &r, n ? bad : nullptr));
   fr_mont_to_bytes((uint8_t*)out32, r, scalar_fmt);
   return BP_OK;
 }
@@ -45,8 +47,12 @@ static int poly_addsub(bp_ctx* ctx, const void* a, size_t na, const void* b, siz
   BP_TRY(upload_fr(ctx, "io.poly_a", a, na, na, BP_FR_MONT, &da));
   BP_TRY(upload_fr(ctx, "io.poly_b", b, nb, nb, BP_FR_MONT, &db));
   BP_TRY(ws_get(ctx, "io.poly_out", n * sizeof(fr_t), (void**)&dout));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, fmt, &bad));                         // ... but they are still looked at
+  BP_TRY(fr_flag_noncanonical_run(ctx, da, na, bad));
+  BP_TRY(fr_flag_noncanonical_run(ctx, db, nb, bad));
   BP_TRY(fr_binary_run(ctx, da, na, db, nb, dout, n, op));
-  return download_fr(ctx, dout, out, n, BP_FR_MONT);
+  return download_fr(ctx, dout, out, n, BP_FR_MONT, bad);
 }
 int bp_poly_add(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, int basis, int scalar_fmt, void* out, size_t* n_out) {
   return poly_addsub(ctx, a, na, b, nb, basis, scalar_fmt, out, n_out, 0);
@@ -64,7 +70,9 @@ int bp_poly_scalar_op(bp_ctx* ctx, const void* a, size_t n, int basis, const voi
   if (!fr_bytes_to_mont(s, (const uint8_t*)s32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   DeviceGuard guard(ctx->device);
   fr_t *da, *dout;
-  BP_TRY(upload_fr(ctx, "io.poly_a", a, n, n, scalar_fmt, &da));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  BP_TRY(upload_fr(ctx, "io.poly_a", a, n, n, scalar_fmt, &da, bad));
   BP_TRY(ws_get(ctx, "io.poly_out", n * sizeof(fr_t), (void**)&dout));
   if (op == 2) {
     BP_TRY(fr_scalar_run(ctx, da, s, dout, n, 2));
@@ -74,7 +82,7 @@ int bp_poly_scalar_op(bp_ctx* ctx, const void* a, size_t n, int basis, const voi
   } else {
     BP_TRY(fr_scalar_run(ctx, da, s, dout, n, 0));           // Lagrange: += rhs for Add AND Sub (polynomial.rs:126-128)
   }
-  return download_fr(ctx, dout, out, n, scalar_fmt);
+  return download_fr(ctx, dout, out, n, scalar_fmt, bad);
 }
 
 int bp_poly_mul(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, int basis, int scalar_fmt, void* out, size_t* n_out) {
@@ -93,12 +101,14 @@ int bp_poly_mul(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb,
   BP_HIP(ctx, hipMemsetAsync(d, 0, 2 * N * sizeof(fr_t), ctx->stream));
   BP_HIP(ctx, hipMemcpyAsync(d, a, na * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
   BP_HIP(ctx, hipMemcpyAsync(d + N, b, nb * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-  if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, 2 * N, 0));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, d, 2 * N, 0, bad));
   BP_TRY(ntt_run(ctx, d, k, 0, 2, N));                        // evaluate both at the N roots (polynomial.rs:255-260)
   BP_TRY(fr_binary_run(ctx, d, N, d + N, N, d, N, 2));        // pointwise product (:262-266)
   BP_TRY(ntt_run(ctx, d, k, 1, 1, N));                        // i_ntt_381 (:270)
   *n_out = target;                                            // [0 ..= n+m] (:272)
-  return download_fr(ctx, d, out, target, scalar_fmt);
+  return download_fr(ctx, d, out, target, scalar_fmt, bad);
 }
 
 int bp_poly_div(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb, int basis, int scalar_fmt, void* out, size_t* n_out) {
@@ -115,8 +125,10 @@ int bp_poly_div(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb,
   const size_t nq = na - nb + 1;
   DeviceGuard guard(ctx->device);
   fr_t *da, *db, *dq;
-  BP_TRY(upload_fr(ctx, "io.poly_a", a, na, na, scalar_fmt, &da));
-  BP_TRY(upload_fr(ctx, "io.poly_b", b, nb, nb, scalar_fmt, &db));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  BP_TRY(upload_fr(ctx, "io.poly_a", a, na, na, scalar_fmt, &da, bad));
+  BP_TRY(upload_fr(ctx, "io.poly_b", b, nb, nb, scalar_fmt, &db, bad));
   BP_TRY(ws_get(ctx, "io.poly_out", nq * sizeof(fr_t), (void**)&dq));
   fr_t b0, b_lead;
   if (!fr_bytes_to_mont(b0, (const uint8_t*)&hb[0], scalar_fmt) || !fr_bytes_to_mont(b_lead, (const uint8_t*)&hb[nb - 1], scalar_fmt))
@@ -125,7 +137,7 @@ int bp_poly_div(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb,
   for (size_t i = 1; i + 1 < nb && binomial; i++) binomial = big_is_zero(hb[i]);
   BP_TRY(poly_div_run(ctx, da, na, db, nb, b0, b_lead, binomial, dq, nq));
   std::vector<fr_t> q(nq);
-  BP_TRY(download_fr(ctx, dq, q.data(), nq, scalar_fmt));
+  BP_TRY(download_fr(ctx, dq, q.data(), nq, scalar_fmt, bad));
   // The reference inserts one quotient coefficient per loop turn and pops every newly zero leading remainder
   // term (polynomial.rs:371-376): its result is the true quotient with the zero coefficients squeezed out.
   fr_t* o = (fr_t*)out;
@@ -248,6 +260,13 @@ int bp_poly_evaluate_device(bp_ctx* ctx, const void* d_coeffs, size_t n, int bas
   memcpy(out32_mont, &r, 32);
   return BP_OK;
 }
+int bp_poly_last_stats(bp_ctx* ctx, uint32_t* div_path, uint64_t* chunks, uint32_t* segments) {
+  if (!ctx) return BP_ERR_INVALID_ARG;
+  if (div_path) *div_path = ctx->poly_div_path;
+  if (chunks) *chunks = ctx->poly_div_chunks;
+  if (segments) *segments = ctx->poly_div_segments;
+  return BP_OK;
+}
 int bp_poly_scale_powers_device(bp_ctx* ctx, const void* d_a, size_t n, const void* w32_mont, void* d_out) {
   if (!ctx || !w32_mont || (n && (!d_a || !d_out))) return BP_ERR_INVALID_ARG;
   fr_t w;
@@ -321,9 +340,12 @@ int bp_grand_product(bp_ctx* ctx, const void* a, const void* b, const void* c, c
   BP_TRY(ws_get(ctx, "io.gp_cols", 7 * n * sizeof(fr_t), (void**)&cols));
   const void* src[6] = {a, b, c, s1, s2, s3};
   for (int j = 0; j < 6; j++) BP_HIP(ctx, hipMemcpyAsync(cols + (size_t)j * n, src[j], n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-  if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, cols, 6 * n, 0));
+  uint32_t* bad;
+  BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
+  if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, cols, 6 * n, 0, bad));
   fr_t* z = cols + 6 * n;
-  BP_TRY(grand_product_run(ctx, cols, cols + n, cols + 2 * n, cols + 3 * n, cols + 4 * n, cols + 5 * n, n, beta, gamma, k1, k2, root, z));
+  BP_TRY(grand_product_run(ctx, cols, cols + n, cols + 2 * n, cols + 3 * n, cols + 4 * n, cols + 5 * n, n, beta, gamma, k1, k2, root, z, nullptr,
+                           bad));
   return download_fr(ctx, z, z_out, n, scalar_fmt);
 }
 

@@ -158,6 +158,10 @@ struct bp_ctx {
   bool ntt_async_pending = false;  // bp_ntt_fr_device_async enqueued a transform whose events have not been read yet
   uint32_t ntt_passes = 0;
   uint32_t ntt_members = 1;       // members of a group context that took part in the last host transform
+  // which path the last poly_div_run took (bp_poly_last_stats): 0 general, 1 binomial local only, 2 plain carry, 3 workgroup carry,
+  // 4 segmented; its chunks per chain (0 on the general path) and segment count G (0 unless segmented)
+  uint32_t poly_div_path = 0, poly_div_segments = 0;
+  uint64_t poly_div_chunks = 0;
   // one process per GPU (capi_comm.hip): the RCCL communicator of this context (ncclComm_t), created by bp_comm_init_rank
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;
@@ -281,10 +285,14 @@ bool ntt_split_ok(uint32_t log_n, uint32_t parts);
 void ntt_split_shape(uint32_t log_n, uint32_t* l1);
 int ntt_tmp_buffer(bp_ctx* ctx, uint32_t log_n, fr_t** out);
 int ntt_run_part(bp_ctx* ctx, fr_t* d_data, uint32_t log_n, int inverse, size_t batch, size_t stride, int phase, uint32_t part, uint32_t parts);
-int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir);
+// d_bad (dir 0 only): device word raised to 1 when an input is >= q (Scalar::from_bytes rejects it, scalar.rs:264-288); nullptr = unchecked
+int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir, uint32_t* d_bad = nullptr);
+// the same test without the conversion; row != 0: the n elements lie in rows of `row`, row b at d + b * stride
+int fr_flag_noncanonical_run(bp_ctx* ctx, const fr_t* d, size_t n, uint32_t* d_bad, size_t row = 0, size_t stride = 0);
+int fr_bad_word(bp_ctx* ctx, int fmt, uint32_t** d_bad);      // BP_FR_BYTES_LE: the context's word, zeroed on the stream; else nullptr
 int fr_binary_run(bp_ctx* ctx, const fr_t* a, size_t na, const fr_t* b, size_t nb, fr_t* out, size_t n, int op);
 int fr_scalar_run(bp_ctx* ctx, const fr_t* a, const fr_t& s, fr_t* out, size_t n, int op);
-int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr_t* host_out);
+int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr_t* host_out, const uint32_t* d_bad = nullptr);
 int poly_eval_many_run(bp_ctx* ctx, int k, const fr_t* const* d_coeffs, const size_t* n, const fr_t* x, fr_t* host_out);
 int poly_div_run(bp_ctx* ctx, fr_t* d_a, size_t na, const fr_t* d_b, size_t nb, const fr_t& b0, const fr_t& b_lead, bool binomial,
                  fr_t* d_q, size_t nq);
@@ -295,7 +303,7 @@ int fr_synthetic_run(bp_ctx* ctx, fr_t* d_out, size_t n, uint64_t seed);
 int fr_scan_mul_run(bp_ctx* ctx, const fr_t* d_in, size_t n, int reverse, int inclusive, fr_t* d_out, fr_t* d_total);
 int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, const fr_t* s1, const fr_t* s2, const fr_t* s3, size_t n,
                       const fr_t& beta, const fr_t& gamma, const fr_t& k1, const fr_t& k2, const fr_t& root, fr_t* d_z,
-                      const fr_t* d_roots = nullptr);
+                      const fr_t* d_roots = nullptr, const uint32_t* d_bad = nullptr);
 int roots_run(bp_ctx* ctx, const fr_t& w, size_t n, fr_t* d_out);
 int srs_decode_run(bp_ctx* ctx, const uint8_t* d_bytes, size_t n, g1_affine* d_out);
 int srs_encode_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes);

@@ -240,10 +240,24 @@ int ntt_run(bp_ctx* ctx, fr_t* d_data, uint32_t k, int inverse, size_t batch, si
   return ntt_run_part(ctx, d_data, k, inverse, batch, stride, -1, 0, 1);
 }
 
-int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir) {
+int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir, uint32_t* d_bad) {
   if (n == 0) return BP_OK;
-  hipLaunchKernelGGL(fr_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, dir);
+  hipLaunchKernelGGL(fr_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, dir, dir == 0 ? d_bad : nullptr);
   BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_flag_noncanonical_run(bp_ctx* ctx, const fr_t* d, size_t n, uint32_t* d_bad, size_t row, size_t stride) {
+  if (n == 0 || !d_bad) return BP_OK;
+  if (row == 0) row = stride = n;
+  hipLaunchKernelGGL(fr_flag_noncanonical, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, row, stride, d_bad);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_bad_word(bp_ctx* ctx, int fmt, uint32_t** d_bad) {
+  *d_bad = nullptr;
+  if (fmt != BP_FR_BYTES_LE) return BP_OK;
+  BP_TRY(ws_get(ctx, "io.fr_bad", 16, (void**)d_bad));
+  BP_HIP(ctx, hipMemsetAsync(*d_bad, 0, 4, ctx->stream));
   return BP_OK;
 }
 int fr_binary_run(bp_ctx* ctx, const fr_t* a, size_t na, const fr_t* b, size_t nb, fr_t* out, size_t n, int op) {

@@ -494,12 +494,28 @@ __global__ void __launch_bounds__(256) fr_synthetic(fr_t* __restrict__ out, size
   store_fr(&out[i], d0);
 }
 // in-place conversion between 32-byte LE canonical and Montgomery limbs (dir 0: to Montgomery, 1: from)
-__global__ void __launch_bounds__(256) fr_convert(fr_t* __restrict__ a, size_t n, int dir) {
+// dir 0 with bad != nullptr: *bad becomes 1 when an input is not canonical (>= q); the caller reads the word with the copy that ends its call
+__device__ __forceinline__ bool fr_is_canonical(const fr_t& x) {
+  fr_t t;
+  return big_sub(t, x, Fr::modulus()) != 0;
+}
+__global__ void __launch_bounds__(256) fr_convert(fr_t* __restrict__ a, size_t n, int dir, uint32_t* __restrict__ bad) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   fr_t x = load_fr(&a[i]), r;
-  if (dir == 0) Fr::to_mont(r, x); else Fr::from_mont(r, x);
+  if (dir == 0) {
+    if (bad && !fr_is_canonical(x)) atomicMax(bad, 1u);
+    Fr::to_mont(r, x);
+  } else Fr::from_mont(r, x);
   store_fr(&a[i], r);
+}
+// the same test alone, for canonical vectors that need no conversion (add / sub commute with the Montgomery map) and for rows
+// with unused memory between them: n elements in rows of `row`, row b at a + b * stride
+__global__ void __launch_bounds__(256) fr_flag_noncanonical(const fr_t* __restrict__ a, size_t n, size_t row, size_t stride, uint32_t* __restrict__ bad) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t x = load_fr(&a[(i / row) * stride + i % row]);
+  if (!fr_is_canonical(x)) atomicMax(bad, 1u);
 }
 
 }  // namespace bp

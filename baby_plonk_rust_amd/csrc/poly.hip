@@ -10,7 +10,7 @@ namespace bp {
 
 // coeffs_evaluate (polynomial.rs:34-45): sum_i c_i x^i.  The reference spends one 256-bit pow per term;
 // the sum is the same field element however it is associated.
-int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr_t* host_out) {
+int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr_t* host_out, const uint32_t* d_bad) {
   if (n == 0) {
     *host_out = Fr::zero();
     return BP_OK;
@@ -26,7 +26,10 @@ int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr
   hipLaunchKernelGGL(fr_sum_small, dim3(1), dim3(256), 256 * sizeof(fr_t), ctx->stream, partial, blocks, result);
   BP_HIP(ctx, hipGetLastError());
   BP_HIP(ctx, hipMemcpyAsync(host_out, result, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t bad = 0;
+  if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
+  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);
   return BP_OK;
 }
 
@@ -69,6 +72,9 @@ int poly_div_run(bp_ctx* ctx, fr_t* d_a, size_t na, const fr_t* d_b, size_t nb, 
                  fr_t* d_q, size_t nq) {
   fr_t lead_inv;
   fr_invert(lead_inv, b_lead);
+  ctx->poly_div_path = 0;
+  ctx->poly_div_chunks = 0;
+  ctx->poly_div_segments = 0;
   if (binomial) {
     const size_t m = nb - 1;
     fr_t f;
@@ -81,12 +87,16 @@ int poly_div_run(bp_ctx* ctx, fr_t* d_a, size_t na, const fr_t* d_b, size_t nb, 
     BP_TRY(ws_get(ctx, "poly.div_head", chunks * m * sizeof(fr_t), (void**)&head));
     BP_TRY(ws_get(ctx, "poly.div_carry", chunks * m * sizeof(fr_t), (void**)&carry));
     const size_t lanes = m * chunks;
+    ctx->poly_div_path = 1;
+    ctx->poly_div_chunks = chunks;
     hipLaunchKernelGGL(poly_div_binomial_local, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, d_a, nq, m, f,
                        lead_inv, K, chunks, d_q, head);
     if (chunks > 1) {
       if (chunks > 4096 && m <= 16) {        // very long chains (x - zeta at 2^20): G segments per chain, a workgroup each
         uint32_t G = (uint32_t)((chunks + 1023) / 1024);
         if (G > 64) G = 64;
+        ctx->poly_div_path = 4;
+        ctx->poly_div_segments = G;
         fr_t *seg_map, *seg_carry;
         BP_TRY(ws_get(ctx, "poly.div_seg_map", 2 * m * G * sizeof(fr_t), (void**)&seg_map));
         BP_TRY(ws_get(ctx, "poly.div_seg_carry", m * G * sizeof(fr_t), (void**)&seg_carry));
@@ -95,12 +105,15 @@ int poly_div_run(bp_ctx* ctx, fr_t* d_a, size_t na, const fr_t* d_b, size_t nb, 
         hipLaunchKernelGGL(poly_div_seg_scan, dim3((unsigned)m), dim3(64), 0, ctx->stream, G, seg_map, seg_carry);
         hipLaunchKernelGGL(poly_div_binomial_carry_seg<1>, dim3((unsigned)m, G), dim3(1024), 2048 * sizeof(fr_t), ctx->stream, nq, m, f, K, chunks, G,
                            head, seg_map, seg_carry, carry);
-      } else if (chunks > 64 && m <= 4096)   // long chains: a workgroup per chain
+      } else if (chunks > 64 && m <= 4096) {  // long chains: a workgroup per chain
+        ctx->poly_div_path = 3;
         hipLaunchKernelGGL(poly_div_binomial_carry_wg, dim3((unsigned)m), dim3(1024), 2048 * sizeof(fr_t), ctx->stream, nq, m, f, K, chunks,
                            head, carry);
-      else
+      } else {
+        ctx->poly_div_path = 2;
         hipLaunchKernelGGL(poly_div_binomial_carry, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, nq, m, f, K, chunks,
                            head, carry);
+      }
       hipLaunchKernelGGL(poly_div_binomial_apply, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, nq, m, f, K, chunks,
                          carry, d_q);
     }
@@ -169,7 +182,8 @@ int fr_scan_mul_run(bp_ctx* ctx, const fr_t* d_in, size_t n, int reverse, int in
 
 // prover.rs:279-319 on device-resident Montgomery columns; d_z receives n values (z_0 .. z_{n-1})
 int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, const fr_t* s1, const fr_t* s2, const fr_t* s3, size_t n,
-                      const fr_t& beta, const fr_t& gamma, const fr_t& k1, const fr_t& k2, const fr_t& root, fr_t* d_z, const fr_t* d_roots) {
+                      const fr_t& beta, const fr_t& gamma, const fr_t& k1, const fr_t& k2, const fr_t& root, fr_t* d_z, const fr_t* d_roots,
+                      const uint32_t* d_bad) {
   if (n == 0) return BP_OK;
   fr_t *roots, *num, *den, *pn, *sd, *totals;
   if (d_roots) roots = const_cast<fr_t*>(d_roots);           // the caller keeps roots_of_unity(n) resident (read-only here)
@@ -186,7 +200,10 @@ int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, 
   BP_TRY(fr_scan_mul_run(ctx, den, n, 1, 1, sd, totals + 1));                  // inclusive suffix products of the denominators
   fr_t h_tot[2];
   BP_HIP(ctx, hipMemcpyAsync(h_tot, totals, 2 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t bad = 0;
+  if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
+  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);      // before the products of such input are judged
   if (big_is_zero(h_tot[1])) return fail(ctx, BP_ERR_DIV_ZERO, "round 2: a permutation denominator is zero (invert().unwrap())", hipSuccess, __FILE__, __LINE__);
   if (!big_eq(h_tot[0], h_tot[1])) return fail(ctx, BP_ERR_ASSERT, "round 2: z_n != 1 (prover.rs:319)", hipSuccess, __FILE__, __LINE__);
   fr_t td_inv;

@@ -36,6 +36,10 @@
  *                        (bp_msm_g1_blob_device + bp_msm_blobs_combine remain for hosts that bring their own collective.)
  *   - wire formats are the reference's own:
  *       scalar  fmt BP_FR_BYTES_LE : 32-byte little-endian canonical  (Scalar::to_bytes,  scalar.rs:292-304)
+ *                                    a value >= q, as a scalar argument or as an element of a vector argument, is
+ *                                    BP_ERR_BAD_SCALAR (Scalar::from_bytes rejects it, scalar.rs:264-288); for a vector the
+ *                                    check runs on the device with the conversion (bp_poly_*, bp_grand_product, bp_ntt_fr on a
+ *                                    single-device context), so the output buffer is unspecified after that error
  *               fmt BP_FR_MONT     : 4 x u64 Montgomery limbs          (Scalar::to_array,  scalar.rs:35-40)
  *       point   96-byte uncompressed affine, x||y big-endian, bit 6 of byte 0 = infinity
  *                                                                      (G1Affine::to_uncompressed, g1.rs:246-260)
@@ -336,7 +340,9 @@ int  bp_grand_product(bp_ctx* ctx, const void* a, const void* b, const void* c, 
 
 /* ---- the same operators on HBM-resident data (Montgomery limbs) -------------------
  * d_* are device pointers (hipMalloc / torch CUDA tensors); scalars and results of O(1) size stay on the host.
- * Semantics, length rules, quirks and error codes are those of the host-pointer entry points above. */
+ * Semantics, length rules, quirks and error codes are those of the host-pointer entry points above.
+ * add, sub and scalar_op are element-wise: d_out may be d_a (or d_b) itself, in place; any other overlap, and any overlap in the
+ * other entry points, is not allowed. */
 int  bp_poly_add_device(bp_ctx* ctx, const void* d_a, size_t na, const void* d_b, size_t nb, int basis, void* d_out, size_t* n_out);
 int  bp_poly_sub_device(bp_ctx* ctx, const void* d_a, size_t na, const void* d_b, size_t nb, int basis, void* d_out, size_t* n_out);
 int  bp_poly_scalar_op_device(bp_ctx* ctx, const void* d_a, size_t n, int basis, const void* s32_mont, int op, void* d_out);
@@ -345,6 +351,11 @@ int  bp_poly_div_device(bp_ctx* ctx, const void* d_a, size_t na, const void* d_b
 int  bp_poly_evaluate_device(bp_ctx* ctx, const void* d_coeffs, size_t n, int basis, const void* x32_mont, void* out32_mont);
 /* out[i] = a[i] * w^i, i.e. p(x) -> p(w x)  (prover.rs:661-674 monomial_z_to_z_omega) */
 int  bp_poly_scale_powers_device(bp_ctx* ctx, const void* d_a, size_t n, const void* w32_mont, void* d_out);
+/* Which kernels the last bp_poly_div / bp_poly_div_device of this context ran (no timing, nothing waited for).  div_path: 0 general
+ * long division, or for a binomial divisor b0 + bm x^m with chunks = ceil(ceil(nq / m) / 32) chunks per chain: 1 one chunk (no carry),
+ * 2 carries by one lane per chain, 3 by one workgroup per chain, 4 by `segments` workgroups per chain.  chunks is 0 on the general
+ * path, segments is 0 on every path but 4.  Any pointer may be null. */
+int  bp_poly_last_stats(bp_ctx* ctx, uint32_t* div_path, uint64_t* chunks, uint32_t* segments);
 int  bp_roots_of_unity_device(bp_ctx* ctx, uint64_t group_order, void* d_out);
 int  bp_grand_product_device(bp_ctx* ctx, const void* d_a, const void* d_b, const void* d_c, const void* d_s1, const void* d_s2,
                              const void* d_s3, size_t n, const void* beta32, const void* gamma32, const void* k1_32,

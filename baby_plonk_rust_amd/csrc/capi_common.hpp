@@ -4,12 +4,11 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "host_codec.hpp"
 
 inline bool fmt_ok(int fmt) { return fmt == BP_FR_BYTES_LE || fmt == BP_FR_MONT; }
 inline bool basis_ok(int b) { return b == BP_BASIS_LAGRANGE || b == BP_BASIS_MONOMIAL; }
 // capi_ctx.hip
-bool fr_bytes_to_mont(bp::fr_t& out, const uint8_t* b32, int fmt);
-void fr_mont_to_bytes(uint8_t* b32, const bp::fr_t& v, int fmt);
 // d_bad (bp::fr_bad_word): upload_fr raises it for a canonical-bytes input >= q; download_fr reads it with the copy that ends the
 // call and returns BP_ERR_BAD_SCALAR when it is set (`host` is then unspecified)
 int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, bp::fr_t** out, uint32_t* d_bad = nullptr);
@@ -18,7 +17,6 @@ int download_fr(bp_ctx* ctx, bp::fr_t* d, void* host, size_t n, int fmt, const u
 void over_members(bp_ctx* ctx, size_t R, const std::function<bool(size_t)>& use, const std::function<void(size_t)>& work);
 void shard_range(size_t n, size_t r, size_t R, size_t* lo, size_t* hi);
 std::vector<bp_ctx*> shards_of(bp_ctx* ctx);
-int lift(bp_ctx* ctx, bp_ctx* member, int rc);
 int ctx_create(bp_ctx** out, int device_id);
 // capi_srs.hip
 int srs_find(bp_ctx* ctx, uint64_t handle, bp::SrsEntry** out);
@@ -37,5 +35,3 @@ int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, siz
 int srs_shards_checked(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, std::vector<SrsShard>* out);
 // does an MSM of n points against this entry go through its fixed-base tables?
 bool srs_tables_pay(const bp::SrsEntry& e, size_t n);
-// capi_ntt.hip
-bool host_root_of_unity(bp::fr_t& out, uint64_t group_order);

@@ -1,5 +1,5 @@
 // capi_ctx.hip -- C ABI of include/bp_msm_ntt.h, part 1: contexts (bp_init / bp_init_multi / streams), workspaces, the member
-// threads of a group context, and the O(1)/O(W) host epilogues (Horner over window sums, affine normalisation, wire encodings).
+// threads of a group context.  (Wire encodings: host_codec.hpp; the Horner passes over an MSM's window sums: msm.hip.)
 // All O(N) work runs in the HIP kernels of msm.hip / ntt.hip / poly.hip / srs.hip / prover.hip; there is no CPU fallback for it.
 #include <stdlib.h>
 #include <string.h>
@@ -80,123 +80,7 @@ int pinned_get(bp_ctx* ctx, size_t bytes, void** out) {
   return BP_OK;
 }
 
-// result = sum_w 2^(c*w) * T_w, most significant window first (the reference's combine, msm.rs:107-115)
-void host_horner(g1_proj& out, const g1_proj* window_sums, uint32_t W, uint32_t c) {
-  g1_proj acc = window_sums[W - 1];
-  for (uint32_t w = W - 1; w-- > 0;) {
-    for (uint32_t d = 0; d < c; d++) g1_double(acc, acc);
-    g1_add(acc, acc, window_sums[w]);
-  }
-  out = acc;
-}
-
-// quads[w * nq + j] = the part of window w's sum that carries the factor 2^(4j) (msm_planes_window_quads):
-//   out = sum_w 2^(c w) sum_j 2^(4 j) quads[w][j], one Horner pass from the top position down -- c (W - 1) + 4 (nq - 1) doublings, the same
-//   dependent chain the W window sums needed (nq = 1 is host_horner: one value per window)
-void host_quad_horner(g1_proj& out, const g1_proj* quads, uint32_t W, uint32_t c, uint32_t nq) {
-  g1_proj acc = g1_identity();
-  uint32_t prev = 0;
-  bool first = true;
-  for (uint32_t w = W; w-- > 0;)
-    for (uint32_t j = nq; j-- > 0;) {
-      const uint32_t pos = c * w + 4 * j;
-      if (first) {
-        acc = quads[(size_t)w * nq + j];
-        first = false;
-      } else {
-        for (uint32_t d = pos; d < prev; d++) g1_double(acc, acc);
-        g1_add(acc, acc, quads[(size_t)w * nq + j]);
-      }
-      prev = pos;
-    }
-  out = acc;
-}
-
-// planes[w * c + 0] = A_w, planes[w * c + 1 + j] = T_{w,j} (j < c - 1):
-//   out = sum_w 2^(c w) (A_w + sum_j 2^j T_{w,j}),  one pass from the top bit position down (bucket b holds digit b + 1);
-//   odd_digits (NAF tables, one window): bucket b holds digit 2b + 1, out = A + 2 sum_j 2^j T_j
-void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, uint32_t c, bool odd_digits) {
-  g1_proj acc = g1_identity();
-  for (uint32_t w = W; w-- > 0;) {
-    const g1_proj* p = planes + (size_t)w * c;
-    for (uint32_t j = c; j-- > 0;) {
-      g1_double(acc, acc);
-      if (j + 1 < c) g1_add(acc, acc, p[1 + j]);           // bit position c - 1 of the window carries no plane
-    }
-    if (odd_digits) g1_double(acc, acc);
-    g1_add(acc, acc, p[0]);
-  }
-  out = acc;
-}
-
-static void fp_to_be48_host(uint8_t* b, const fp_t& a) {
-  for (int i = 0; i < 12; i++) {
-    uint8_t* p = b + 4 * (11 - i);
-    p[0] = (uint8_t)(a.l[i] >> 24); p[1] = (uint8_t)(a.l[i] >> 16); p[2] = (uint8_t)(a.l[i] >> 8); p[3] = (uint8_t)a.l[i];
-  }
-}
-static fp_t fp_from_be48_host(const uint8_t* b) {
-  fp_t r;
-  for (int i = 0; i < 12; i++) {
-    const uint8_t* p = b + 4 * (11 - i);
-    r.l[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
-  }
-  return r;
-}
-// G1Affine::from(p).to_uncompressed()  (g1.rs:49-63, 246-260)
-void host_encode96(uint8_t out96[96], const g1_proj& p) {
-  memset(out96, 0, 96);
-  if (g1_is_identity(p)) {
-    out96[0] = 0x40;
-    return;
-  }
-  g1_affine a = g1_to_affine(p);
-  fp_t x, y;
-  Fp::from_mont(x, a.x);
-  Fp::from_mont(y, a.y);
-  fp_to_be48_host(out96, x);
-  fp_to_be48_host(out96 + 48, y);
-}
-// G1Affine::from_uncompressed_unchecked (g1.rs:273-322) without the curve check
-bool host_decode96(g1_proj& out, const uint8_t in96[96]) {
-  uint8_t buf[96];
-  memcpy(buf, in96, 96);
-  const uint32_t flags = buf[0] >> 5;
-  buf[0] &= 0x1f;
-  fp_t x = fp_from_be48_host(buf), y = fp_from_be48_host(buf + 48), t;
-  if (!big_sub(t, x, Fp::modulus()) || !big_sub(t, y, Fp::modulus())) return false;
-  if (flags & 0b101) return false;
-  if (flags & 0b010) {
-    if (!big_is_zero(x) || !big_is_zero(y)) return false;
-    out = g1_identity();
-    return true;
-  }
-  Fp::to_mont(out.x, x);
-  Fp::to_mont(out.y, y);
-  out.z = Fp::one();
-  return true;
-}
-
 }  // namespace bp
-
-// ------------------------------------------------------------------------------------------------------
-bool fr_bytes_to_mont(fr_t& out, const uint8_t* b32, int fmt) {
-  fr_t v;
-  memcpy(&v, b32, 32);
-  if (fmt == BP_FR_MONT) {
-    out = v;
-    return true;
-  }
-  fr_t t;
-  if (!big_sub(t, v, Fr::modulus())) return false;       // >= q: Scalar::from_bytes rejects (scalar.rs:264-288)
-  Fr::to_mont(out, v);
-  return true;
-}
-void fr_mont_to_bytes(uint8_t* b32, const fr_t& v, int fmt) {
-  fr_t t = v;
-  if (fmt == BP_FR_BYTES_LE) Fr::from_mont(t, v);
-  memcpy(b32, &t, 32);
-}
 
 // upload n scalars to workspace `name`, converting to Montgomery form on the device if needed
 int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t cap_elems, int fmt, fr_t** out, uint32_t* d_bad) {
@@ -298,12 +182,6 @@ std::vector<bp_ctx*> shards_of(bp_ctx* ctx) {
   if (is_group(ctx)) return ctx->members;
   return std::vector<bp_ctx*>(1, ctx);
 }
-// a member's failure is reported on the context the caller holds
-int lift(bp_ctx* ctx, bp_ctx* member, int rc) {
-  if (rc != BP_OK && member != ctx) ctx->last_error = member->last_error;
-  return rc;
-}
-
 int ctx_create(bp_ctx** out, int device_id) {
   *out = nullptr;
   int count = 0;

@@ -222,19 +222,11 @@ int bp_ntt_last_stats(bp_ctx* ctx, float* device_ms, uint32_t* passes) {
 }
 int bp_ntt_last_members(bp_ctx* ctx) { return ctx ? (int)ctx->ntt_members : BP_ERR_INVALID_ARG; }
 
-// utils.rs:39-43: ROOT_OF_UNITY.pow([2^32 / group_order, 0, 0, 0]) -- integer division, as written
-bool host_root_of_unity(fr_t& out, uint64_t group_order) {
-  if (group_order == 0) return false;                       // division by zero panics in the reference
-  const uint64_t e = ((uint64_t)1 << 32) / group_order;
-  uint32_t e32[2] = {(uint32_t)e, (uint32_t)(e >> 32)};
-  Fr::pow(out, fr_root_of_unity(false), e32, 2);
-  return true;
-}
 int bp_root_of_unity(uint64_t group_order, int scalar_fmt, uint8_t out32[32]) {
   if (!out32 || !fmt_ok(scalar_fmt)) return BP_ERR_INVALID_ARG;
   fr_t w;
   if (!host_root_of_unity(w, group_order)) return BP_ERR_INVALID_ARG;
-  fr_mont_to_bytes(out32, w, scalar_fmt);
+  fr_to_bytes(out32, w, scalar_fmt);
   return BP_OK;
 }
 int bp_roots_of_unity(bp_ctx* ctx, uint64_t group_order, int scalar_fmt, void* out) {
@@ -253,8 +245,8 @@ int bp_fr_convert(const void* in, size_t n, int from_fmt, int to_fmt, void* out)
   if (!fmt_ok(from_fmt) || !fmt_ok(to_fmt) || (n && (!in || !out))) return BP_ERR_INVALID_ARG;
   for (size_t i = 0; i < n; i++) {
     fr_t v;
-    if (!fr_bytes_to_mont(v, (const uint8_t*)in + 32 * i, from_fmt)) return BP_ERR_BAD_SCALAR;
-    fr_mont_to_bytes((uint8_t*)out + 32 * i, v, to_fmt);
+    if (!fr_from_bytes(v, (const uint8_t*)in + 32 * i, from_fmt)) return BP_ERR_BAD_SCALAR;
+    fr_to_bytes((uint8_t*)out + 32 * i, v, to_fmt);
   }
   return BP_OK;
 }

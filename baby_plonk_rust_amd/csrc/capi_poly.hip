@@ -21,14 +21,14 @@ int bp_poly_evaluate(bp_ctx* ctx, const void* coeffs, size_t n, int basis, const
   if (!ctx || !x32 || !out32 || !fmt_ok(scalar_fmt) || !basis_ok(basis) || (n && !coeffs)) return BP_ERR_INVALID_ARG;
   if (basis != BP_BASIS_MONOMIAL) return fail(ctx, BP_ERR_BASIS, "coeffs_evaluate needs the Monomial basis", hipSuccess, __FILE__, __LINE__);
   fr_t x, r;
-  if (!fr_bytes_to_mont(x, (const uint8_t*)x32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
+  if (!fr_from_bytes(x, (const uint8_t*)x32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   DeviceGuard guard(ctx->device);
   fr_t* d;
   uint32_t* bad;
   BP_TRY(fr_bad_word(ctx, scalar_fmt, &bad));
   BP_TRY(upload_fr(ctx, "io.poly_a", coeffs, n, n, scalar_fmt, &d, bad));
   BP_TRY(poly_eval_run(ctx, d, n, x, &r, n ? bad : nullptr));
-  fr_mont_to_bytes((uint8_t*)out32, r, scalar_fmt);
+  fr_to_bytes((uint8_t*)out32, r, scalar_fmt);
   return BP_OK;
 }
 
@@ -67,7 +67,7 @@ int bp_poly_scalar_op(bp_ctx* ctx, const void* a, size_t n, int basis, const voi
   if (n == 0) return op == 2 || basis == BP_BASIS_LAGRANGE ? BP_OK
                                                            : fail(ctx, BP_ERR_INVALID_ARG, "empty polynomial", hipSuccess, __FILE__, __LINE__);
   fr_t s;
-  if (!fr_bytes_to_mont(s, (const uint8_t*)s32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
+  if (!fr_from_bytes(s, (const uint8_t*)s32, scalar_fmt)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   DeviceGuard guard(ctx->device);
   fr_t *da, *dout;
   uint32_t* bad;
@@ -131,7 +131,7 @@ int bp_poly_div(bp_ctx* ctx, const void* a, size_t na, const void* b, size_t nb,
   BP_TRY(upload_fr(ctx, "io.poly_b", b, nb, nb, scalar_fmt, &db, bad));
   BP_TRY(ws_get(ctx, "io.poly_out", nq * sizeof(fr_t), (void**)&dq));
   fr_t b0, b_lead;
-  if (!fr_bytes_to_mont(b0, (const uint8_t*)&hb[0], scalar_fmt) || !fr_bytes_to_mont(b_lead, (const uint8_t*)&hb[nb - 1], scalar_fmt))
+  if (!fr_from_bytes(b0, (const uint8_t*)&hb[0], scalar_fmt) || !fr_from_bytes(b_lead, (const uint8_t*)&hb[nb - 1], scalar_fmt))
     return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   bool binomial = nb >= 2;
   for (size_t i = 1; i + 1 < nb && binomial; i++) binomial = big_is_zero(hb[i]);
@@ -331,8 +331,8 @@ int bp_grand_product(bp_ctx* ctx, const void* a, const void* b, const void* c, c
   if (n == 0) return BP_OK;
   if (n > ((size_t)1 << 25)) return fail(ctx, BP_ERR_TOO_LARGE, "grand product longer than 2^25", hipSuccess, __FILE__, __LINE__);
   fr_t beta, gamma, k1, k2, root;
-  if (!fr_bytes_to_mont(beta, (const uint8_t*)beta32, scalar_fmt) || !fr_bytes_to_mont(gamma, (const uint8_t*)gamma32, scalar_fmt) ||
-      !fr_bytes_to_mont(k1, (const uint8_t*)k1_32, scalar_fmt) || !fr_bytes_to_mont(k2, (const uint8_t*)k2_32, scalar_fmt))
+  if (!fr_from_bytes(beta, (const uint8_t*)beta32, scalar_fmt) || !fr_from_bytes(gamma, (const uint8_t*)gamma32, scalar_fmt) ||
+      !fr_from_bytes(k1, (const uint8_t*)k1_32, scalar_fmt) || !fr_from_bytes(k2, (const uint8_t*)k2_32, scalar_fmt))
     return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
   host_root_of_unity(root, n);                                   // roots_of_unity(group_order), utils.rs:45-52
   DeviceGuard guard(ctx->device);

@@ -119,7 +119,7 @@ int bp_prove(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, const vo
   (void)srs;      // an SRS shorter than group_order + 6 powers truncates the commitments exactly as Setup::commit's zip does (msm.rs:29)
   fr_t blind[11];
   for (int j = 0; j < 11; j++)
-    if (!fr_bytes_to_mont(blind[j], blinders + 32 * j, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "blinder >= q", hipSuccess, __FILE__, __LINE__);
+    if (!fr_from_bytes(blind[j], blinders + 32 * j, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "blinder >= q", hipSuccess, __FILE__, __LINE__);
   DeviceGuard guard(ctx->device);
   fr_t* wit;
   BP_TRY(ws_get(ctx, "prove.witness", 4 * n * sizeof(fr_t), (void**)&wit));

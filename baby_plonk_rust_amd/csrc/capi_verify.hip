@@ -18,19 +18,13 @@ using namespace bp;
 static const char* const VERIFY_POINT_NAME[VERIFY_POINTS] = {"a_1", "b_1", "c_1", "z_1", "t_lo_1", "t_mid_1", "t_hi_1", "w_zeta_1", "w_zeta_omega_1"};
 static const char* const VERIFY_EVAL_NAME[VERIFY_EVALS] = {"a_bar", "b_bar", "c_bar", "s1_bar", "s2_bar", "z_omega_bar"};
 
-static bool eval_canonical(const uint8_t* b32) {
-  fr_t v, t;
-  memcpy(&v, b32, 32);
-  return big_sub(t, v, Fr::modulus()) != 0;
-}
-
 int bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void* out, size_t* first_bad) {
   if (!fmt_ok(scalar_fmt) || (m && (!proofs624 || !out))) return BP_ERR_INVALID_ARG;
   if (first_bad) *first_bad = SIZE_MAX;
   for (size_t j = 0; j < m; j++) {
     const uint8_t* rec = proofs624 + (size_t)VERIFY_RECORD_BYTES * j;
     for (int k = 0; k < VERIFY_EVALS; k++)
-      if (!eval_canonical(rec + 432 + 32 * k)) {
+      if (!fr_is_canonical(rec + 432 + 32 * k)) {
         if (first_bad) *first_bad = j;
         return BP_ERR_BAD_SCALAR;
       }
@@ -39,8 +33,8 @@ int bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void
     fr_t c[6];
     plonk_challenges(words, c, nullptr);
     for (int k = 0; k < 6; k++) {
-      fr_t v = c[k];
-      if (scalar_fmt == BP_FR_MONT) Fr::to_mont(v, c[k]);
+      fr_t v = c[k];                                           // canonical limbs: the BP_FR_BYTES_LE image as it is
+      if (scalar_fmt == BP_FR_MONT) Fr::to_mont(v, v);
       memcpy((uint8_t*)out + ((size_t)6 * j + k) * 32, &v, 32);
     }
   }
@@ -51,22 +45,13 @@ int bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void
 static bool vk_point_decode(g1_affine& out, const uint8_t in96[96]) {
   g1_proj p;
   if (!host_decode96(p, in96)) return false;
-  if (g1_is_identity(p)) {
-    out.x = Fp::zero();
-    out.y = Fp::zero();
+  if (g1_is_identity(p)) {                                   // only a record with the infinity flag
+    out.x = out.y = Fp::zero();
     return true;
   }
-  fp_t lhs, rhs, b4 = Fp::one();
-  Fp::sqr(lhs, p.y);
-  Fp::sqr(rhs, p.x);
-  Fp::mul(rhs, rhs, p.x);
-  Fp::dbl(b4, b4);
-  Fp::dbl(b4, b4);
-  Fp::add(rhs, rhs, b4);
-  if (!big_eq(lhs, rhs)) return false;
   out.x = p.x;
   out.y = p.y;
-  return true;
+  return g1_affine_on_curve(out);
 }
 
 static void encode_identity_pair(uint8_t out192[192]) {
@@ -93,12 +78,7 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   shared_pts[8] = g1_affine_generator();
   VerifyParams P;
   if (!host_root_of_unity(P.omega, (uint64_t)1 << log_n)) return BP_ERR_INVALID_ARG;
-  {
-    fr_t n = Fr::zero();
-    n.l[log_n >> 5] = 1u << (log_n & 31);
-    Fr::to_mont(n, n);
-    fr_invert(P.n_inv, n);
-  }
+  fr_invert(P.n_inv, fr_from_u64((uint64_t)1 << log_n));
   P.log_n = log_n;
   P.fmt = fmt;
   P.chal_fmt = challenges ? fmt : BP_FR_MONT;

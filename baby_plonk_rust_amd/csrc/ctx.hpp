@@ -215,6 +215,11 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 inline bool is_group(const bp_ctx* ctx) { return ctx->members.size() > 1; }
+// a member's (or a lane's, or a side context's) failure is reported on the context the caller holds
+inline int lift(bp_ctx* ctx, const bp_ctx* member, int rc) {
+  if (rc != BP_OK && member != ctx) ctx->last_error = member->last_error;
+  return rc;
+}
 // does a copy between the leader's memory and member m's cross devices?  (m on another GPU, or a rehearsal group's member)
 inline bool peer_path(const bp_ctx* m, int other_device) {
   if (m->device != other_device) return true;
@@ -333,13 +338,5 @@ int commit_lane_finish(bp_ctx* ctx, int j, const MsmPending& pend, g1_proj* out)
 int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_wit, const fr_t blind[11], uint8_t proof[624], bool pi_zero = false,
               const ProveStaged* staged = nullptr);
 void transcript_test_vector(uint8_t out32[32]);
-
-// ---- host-side helpers (capi_ctx.hip) ---------------------------------------------------
-void host_horner(g1_proj& out, const g1_proj* window_sums, uint32_t W, uint32_t c);
-void host_quad_horner(g1_proj& out, const g1_proj* quads, uint32_t W, uint32_t c, uint32_t nq);
-void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, uint32_t c, bool odd_digits = false);
-void host_encode96(uint8_t out96[96], const g1_proj& p);
-bool host_decode96(g1_proj& out, const uint8_t in96[96]);
-void host_compress48(uint8_t out48[48], const g1_proj& p);
 
 }  // namespace bp

@@ -664,6 +664,46 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   return BP_OK;
 }
 
+// ---- host epilogue: Horner over what the device hands over
+// quads[w * nq + j] = the part of window w's sum that carries the factor 2^(4j) (msm_planes_window_quads):
+//   out = sum_w 2^(c w) sum_j 2^(4 j) quads[w][j], one Horner pass from the top position down -- c (W - 1) + 4 (nq - 1) doublings, the same
+//   dependent chain the W window sums needed (nq = 1: one value per window, the reference's combine, msm.rs:107-115)
+static void host_quad_horner(g1_proj& out, const g1_proj* quads, uint32_t W, uint32_t c, uint32_t nq) {
+  g1_proj acc = g1_identity();
+  uint32_t prev = 0;
+  bool first = true;
+  for (uint32_t w = W; w-- > 0;)
+    for (uint32_t j = nq; j-- > 0;) {
+      const uint32_t pos = c * w + 4 * j;
+      if (first) {
+        acc = quads[(size_t)w * nq + j];
+        first = false;
+      } else {
+        for (uint32_t d = pos; d < prev; d++) g1_double(acc, acc);
+        g1_add(acc, acc, quads[(size_t)w * nq + j]);
+      }
+      prev = pos;
+    }
+  out = acc;
+}
+
+// planes[w * c + 0] = A_w, planes[w * c + 1 + j] = T_{w,j} (j < c - 1):
+//   out = sum_w 2^(c w) (A_w + sum_j 2^j T_{w,j}),  one pass from the top bit position down (bucket b holds digit b + 1);
+//   odd_digits (NAF tables, one window): bucket b holds digit 2b + 1, out = A + 2 sum_j 2^j T_j
+static void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, uint32_t c, bool odd_digits = false) {
+  g1_proj acc = g1_identity();
+  for (uint32_t w = W; w-- > 0;) {
+    const g1_proj* p = planes + (size_t)w * c;
+    for (uint32_t j = c; j-- > 0;) {
+      g1_double(acc, acc);
+      if (j + 1 < c) g1_add(acc, acc, p[1 + j]);           // bit position c - 1 of the window carries no plane
+    }
+    if (odd_digits) g1_double(acc, acc);
+    g1_add(acc, acc, p[0]);
+  }
+  out = acc;
+}
+
 // waits for the stream, checks the scalar status and runs the host epilogue: window sums / planes back to the reference's
 // Montgomery limbs, then Horner (msm.rs:107-115).  The timing stats describe the last launched MSM of this ctx.
 int msm_finish(bp_ctx* ctx, const MsmPending& pend, g1_proj* host_out) {

@@ -20,82 +20,11 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "host_codec.hpp"
 #include "prover_kernels.hpp"
 #include "transcript.hpp"
 
 namespace bp {
-
-// G1Affine::to_compressed (g1.rs:221-244): big-endian x, bit 7 compressed, bit 6 infinity, bit 5 y lexicographically largest
-void host_compress48(uint8_t out[48], const g1_proj& p) {
-  memset(out, 0, 48);
-  if (g1_is_identity(p)) {
-    out[0] = 0xc0;
-    return;
-  }
-  g1_affine a = g1_to_affine(p);
-  fp_t x, y, ny;
-  Fp::from_mont(x, a.x);
-  Fp::from_mont(y, a.y);
-  Fp::neg(ny, a.y);
-  Fp::from_mont(ny, ny);
-  for (int i = 0; i < 12; i++) {
-    uint8_t* q = out + 4 * (11 - i);
-    q[0] = (uint8_t)(x.l[i] >> 24); q[1] = (uint8_t)(x.l[i] >> 16); q[2] = (uint8_t)(x.l[i] >> 8); q[3] = (uint8_t)x.l[i];
-  }
-  bool larger = false;                                       // y > -y  (fp.rs:273-298)
-  for (int i = 11; i >= 0; i--) {
-    if (y.l[i] != ny.l[i]) {
-      larger = y.l[i] > ny.l[i];
-      break;
-    }
-  }
-  out[0] |= 0x80 | (larger ? 0x20 : 0);
-}
-
-// k points at once: their affine forms share ONE field inversion (Montgomery's trick, as G1Projective::batch_normalize does,
-// g1.rs:806-839) -- a Fermat inversion is ~570 field multiplications on the host, ~26 us; the identity (z = 0) is skipped
-static void host_compress48_many(uint8_t* out, const g1_proj* p, int k) {
-  fp_t prefix[16], acc = Fp::one();
-  bool inf[16];
-  for (int j = 0; j < k; j++) {
-    inf[j] = g1_is_identity(p[j]);
-    prefix[j] = acc;
-    if (!inf[j]) Fp::mul(acc, acc, p[j].z);
-  }
-  fp_t inv;
-  fp_invert(inv, acc);
-  for (int j = k; j-- > 0;) {
-    if (inf[j]) {
-      host_compress48(out + 48 * j, p[j]);
-      continue;
-    }
-    fp_t zinv;
-    Fp::mul(zinv, inv, prefix[j]);
-    Fp::mul(inv, inv, p[j].z);
-    g1_affine a;                               // encoded directly from the affine pair (host_compress48 would invert z again)
-    Fp::mul(a.x, p[j].x, zinv);
-    Fp::mul(a.y, p[j].y, zinv);
-    uint8_t* o = out + 48 * j;
-    memset(o, 0, 48);
-    fp_t x, y, ny;
-    Fp::from_mont(x, a.x);
-    Fp::from_mont(y, a.y);
-    Fp::neg(ny, a.y);
-    Fp::from_mont(ny, ny);
-    for (int i = 0; i < 12; i++) {
-      uint8_t* q = o + 4 * (11 - i);
-      q[0] = (uint8_t)(x.l[i] >> 24); q[1] = (uint8_t)(x.l[i] >> 16); q[2] = (uint8_t)(x.l[i] >> 8); q[3] = (uint8_t)x.l[i];
-    }
-    bool larger = false;                       // y > -y  (fp.rs:273-298)
-    for (int i = 11; i >= 0; i--) {
-      if (y.l[i] != ny.l[i]) {
-        larger = y.l[i] > ny.l[i];
-        break;
-      }
-    }
-    o[0] |= 0x80 | (larger ? 0x20 : 0);
-  }
-}
 
 namespace {
 
@@ -105,33 +34,10 @@ fr_t fadd(const fr_t& a, const fr_t& b) { fr_t r; Fr::add(r, a, b); return r; }
 fr_t fsub(const fr_t& a, const fr_t& b) { fr_t r; Fr::sub(r, a, b); return r; }
 fr_t fneg(const fr_t& a) { fr_t r; Fr::neg(r, a); return r; }
 fr_t finv(const fr_t& a) { fr_t r; fr_invert(r, a); return r; }
-fr_t fpow(const fr_t& a, uint64_t e) {
-  uint32_t e32[2] = {(uint32_t)e, (uint32_t)(e >> 32)};
-  fr_t r;
-  Fr::pow(r, a, e32, 2);
-  return r;
-}
-fr_t from_u64(uint64_t v) {
-  fr_t c = Fr::zero(), r;
-  c.l[0] = (uint32_t)v;
-  c.l[1] = (uint32_t)(v >> 32);
-  Fr::to_mont(r, c);
-  return r;
-}
-bool from_le32(fr_t& out, const uint8_t* b32) {             // Scalar::from_bytes (scalar.rs:264-288)
-  fr_t v, t;
-  memcpy(&v, b32, 32);
-  if (!big_sub(t, v, Fr::modulus())) return false;
-  Fr::to_mont(out, v);
-  return true;
-}
-void to_le32(uint8_t* b32, const fr_t& v) {                  // Scalar::to_bytes (scalar.rs:292-304)
-  fr_t t;
-  Fr::from_mont(t, v);
-  memcpy(b32, &t, 32);
-}
-fr_t root_of_unity(uint64_t order) {                         // utils.rs:39-43
-  return fpow(fr_root_of_unity(false), ((uint64_t)1 << 32) / order);
+fr_t root_of_unity(uint64_t order) {                         // order = 2^k here, never 0
+  fr_t w;
+  (void)host_root_of_unity(w, order);
+  return w;
 }
 
 // src/transcript.rs:4-86 (alpha is drawn under the label "z_1", :24; challenges are rejection-sampled until canonical
@@ -146,7 +52,7 @@ struct PlonkTranscript {
   void point48(const char* label, const uint8_t c[48]) { t.append_message(label, c, 48); }       // already compressed
   void scalar(const char* label, const fr_t& v) {
     uint8_t b[32];
-    to_le32(b, v);
+    fr_to_bytes(b, v, BP_FR_BYTES_LE);
     t.append_message(label, b, 32);
   }
   fr_t challenge(const char* label) {
@@ -154,7 +60,7 @@ struct PlonkTranscript {
       uint8_t b[32];
       t.challenge_bytes(label, b, 32);
       fr_t v;
-      if (from_le32(v, b) && !big_is_zero(v)) {
+      if (fr_from_bytes(v, b, BP_FR_BYTES_LE) && !big_is_zero(v)) {
         t.append_message(label, b, 32);
         return v;
       }
@@ -228,7 +134,7 @@ static int circuit_fill(bp_ctx* ctx, const fr_t* d_lag, CircuitEntry& e) {
   BP_HIP(ctx, hipMalloc((void**)&e.g_pow, (n + 8) * sizeof(fr_t)));
   BP_HIP(ctx, hipMalloc((void**)&e.roots, n * sizeof(fr_t)));
   BP_HIP(ctx, hipMalloc((void**)&e.ginv_pow, N * sizeof(fr_t)));
-  const fr_t g = from_u64(COSET_GEN), w4n = root_of_unity(N);
+  const fr_t g = fr_from_u64(COSET_GEN), w4n = root_of_unity(N);
   BP_TRY(roots_run(ctx, g, n + 8, e.g_pow));
   BP_TRY(roots_run(ctx, root_of_unity(n), n, e.roots));
   BP_TRY(roots_run(ctx, finv(g), N, e.ginv_pow));
@@ -244,12 +150,12 @@ static int circuit_fill(bp_ctx* ctx, const fr_t* d_lag, CircuitEntry& e) {
   fr_t* l1;
   BP_TRY(ws_get(ctx, "prove.l1", n * sizeof(fr_t), (void**)&l1));
   BP_HIP(ctx, hipMemsetAsync(l1, 0, n * sizeof(fr_t), ctx->stream));
-  BP_TRY(fr_scalar_run(ctx, l1, finv(from_u64(n)), l1, n, 0));                          // 0 + 1/n
+  BP_TRY(fr_scalar_run(ctx, l1, finv(fr_from_u64(n)), l1, n, 0));                          // 0 + 1/n
   hipLaunchKernelGGL(fr_mul_table_pad, dim3(blocks), dim3(256), 0, ctx->stream, l1, n, e.g_pow, e.coset + (size_t)8 * N, N);
   BP_HIP(ctx, hipGetLastError());
   BP_TRY(ntt_run(ctx, e.coset, log_n + 2, 0, N_PRE, N));
   // 1 / (X^n - 1) on the coset: X^n = g^n i^j for X = g w_4n^j, i = w_4n^n the 4th root of unity
-  const fr_t gn = fpow(g, n), i4 = fpow(w4n, n);
+  const fr_t gn = fr_pow_u64(g, n), i4 = fr_pow_u64(w4n, n);
   fr_t p = Fr::one();
   for (int j = 0; j < 4; j++) {
     e.zh_inv[j] = finv(fsub(fmul(gn, p), Fr::one()));
@@ -298,7 +204,7 @@ int circuit_split_build(bp_ctx* ctx, CircuitEntry& e) {
   const uint32_t k = e.log_n;
   const size_t n = (size_t)1 << k, N = 4 * n;
   const uint32_t used = one_gpu ? 1 : (R >= 4 ? 4 : 2), per = 4 / used;
-  const fr_t g = from_u64(COSET_GEN), w4n = root_of_unity(N);
+  const fr_t g = fr_from_u64(COSET_GEN), w4n = root_of_unity(N);
   fr_t* tmp;
   BP_TRY(ws_get(ctx, "prove.split_tmp", 10 * n * sizeof(fr_t), (void**)&tmp));
   const unsigned blocks = (unsigned)((n + 255) / 256);
@@ -308,13 +214,9 @@ int circuit_split_build(bp_ctx* ctx, CircuitEntry& e) {
     sh.member = m;
     sh.first = r * per;
     sh.count = per;
-    {
-      int rc = side_ctx_get(m, &sh.work);      // a stream, workspace and transform tables of its own on the member's device: the share's work
-      if (rc != BP_OK) {                       // runs beside the member's MSM shards instead of queueing behind them
-        ctx->last_error = m->last_error;
-        return rc;
-      }
-    }
+    // a stream, workspace and transform tables of its own on the member's device: the share's work runs beside the member's MSM
+    // shards instead of queueing behind them
+    BP_TRY(lift(ctx, m, side_ctx_get(m, &sh.work)));
     {
       DeviceGuard guard(m->device);
       hipError_t he = hipMalloc((void**)&sh.pre, (size_t)per * 9 * n * sizeof(fr_t));
@@ -338,13 +240,9 @@ int circuit_split_build(bp_ctx* ctx, CircuitEntry& e) {
       DeviceGuard guard(m->device);
       BP_HIP(ctx, copy_to_member(m, sh.pre + (size_t)c * 9 * n, tmp, ctx->device, (size_t)N_PRE * n));
       BP_HIP(ctx, copy_to_member(m, sh.xs + (size_t)c * n, tmp + (size_t)N_PRE * n, ctx->device, n));
-      const fr_t sj = fmul(g, fpow(w4n, j));
-      int rc = roots_run(m, sj, n, sh.spow + (size_t)c * n);
-      if (rc == BP_OK) rc = roots_run(m, finv(sj), n, sh.sinv + (size_t)c * n);
-      if (rc != BP_OK) {
-        ctx->last_error = m->last_error;
-        return rc;
-      }
+      const fr_t sj = fmul(g, fr_pow_u64(w4n, j));
+      BP_TRY(lift(ctx, m, roots_run(m, sj, n, sh.spow + (size_t)c * n)));
+      BP_TRY(lift(ctx, m, roots_run(m, finv(sj), n, sh.sinv + (size_t)c * n)));
       BP_HIP(ctx, stream_wait(m->stream));    // tmp is reused for the next coset
     }
   }
@@ -363,15 +261,11 @@ static int coset_inputs(bp_ctx* ctx, const CircuitEntry& cir, const CosetShare& 
   const uint32_t k = cir.log_n;
   const size_t n = (size_t)1 << k, N = 4 * n, cap = n + 8;
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  const fr_t g = from_u64(COSET_GEN), w4n = root_of_unity(N), gn = fpow(g, n), i4 = fpow(w4n, n);
+  const fr_t g = fr_from_u64(COSET_GEN), w4n = root_of_unity(N), gn = fr_pow_u64(g, n), i4 = fr_pow_u64(w4n, n);
   bp_ctx* w = sh.work;
   fr_t *cf, *ev;
-  int rc = ws_get(w, "prove.split_coef", 5 * cap * sizeof(fr_t), (void**)&cf);
-  if (rc == BP_OK) rc = ws_get(w, "prove.split_ev", (size_t)sh.count * 5 * n * sizeof(fr_t), (void**)&ev);
-  if (rc != BP_OK) {
-    ctx->last_error = w->last_error;
-    return rc;
-  }
+  BP_TRY(lift(ctx, w, ws_get(w, "prove.split_coef", 5 * cap * sizeof(fr_t), (void**)&cf)));
+  BP_TRY(lift(ctx, w, ws_get(w, "prove.split_ev", (size_t)sh.count * 5 * n * sizeof(fr_t), (void**)&ev)));
   *ev_out = ev;
   BP_HIP(ctx, hipStreamWaitEvent(w->stream, ctx->ev[4], 0));          // the coefficient vectors are ready behind the leader's event
   for (int p = 0; p < 5; p++)
@@ -387,19 +281,15 @@ static int coset_inputs(bp_ctx* ctx, const CircuitEntry& cir, const CosetShare& 
         hipLaunchKernelGGL(fr_fold_scale, dim3(blocks), dim3(256), 0, w->stream, cf + (size_t)p * cap, lens5[p], n, sn, sh.spow + (size_t)c * n, e + (size_t)p * n);
     BP_HIP(ctx, hipGetLastError());
     // contiguous runs of selected slots are transformed together
-    for (int p = 0; p < 5 && rc == BP_OK;) {
+    for (int p = 0; p < 5;) {
       if (!(which >> p & 1)) {
         p++;
         continue;
       }
       int q = p;
       while (q < 5 && (which >> q & 1)) q++;
-      rc = ntt_run(w, e + (size_t)p * n, k, 0, (size_t)(q - p), n);
+      BP_TRY(lift(ctx, w, ntt_run(w, e + (size_t)p * n, k, 0, (size_t)(q - p), n)));
       p = q;
-    }
-    if (rc != BP_OK) {
-      ctx->last_error = w->last_error;
-      return rc;
     }
   }
   return BP_OK;
@@ -421,7 +311,7 @@ static int round3_by_coset(bp_ctx* ctx, const CircuitEntry& cir, const fr_t* con
   const uint32_t k = cir.log_n;
   const size_t n = (size_t)1 << k, N = 4 * n;
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  const fr_t g = from_u64(COSET_GEN), w4n = root_of_unity(N), gn = fpow(g, n), i4 = fpow(w4n, n);
+  const fr_t g = fr_from_u64(COSET_GEN), w4n = root_of_unity(N), gn = fr_pow_u64(g, n), i4 = fr_pow_u64(w4n, n);
   fr_t* v;                                                            // the four residues, one after the other
   BP_TRY(ws_get(ctx, "prove.split_v", 4 * n * sizeof(fr_t), (void**)&v));
   BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));              // z's coefficients (and the others, if not sent early) are ready behind this event
@@ -430,23 +320,15 @@ static int round3_by_coset(bp_ctx* ctx, const CircuitEntry& cir, const fr_t* con
     DeviceGuard guard(w->device);
     fr_t *ev, *tq;
     BP_TRY(coset_inputs(ctx, cir, sh, coefs5, lens5, early_done ? 0x08u : (pi_zero ? 0x0Fu : 0x1Fu), &ev, pi_zero && !early_done));
-    int rc = ws_get(w, "prove.split_tq", n * sizeof(fr_t), (void**)&tq);
-    if (rc != BP_OK) {
-      ctx->last_error = w->last_error;
-      return rc;
-    }
+    BP_TRY(lift(ctx, w, ws_get(w, "prove.split_tq", n * sizeof(fr_t), (void**)&tq)));
     for (uint32_t c = 0; c < sh.count; c++) {
       const uint32_t j = sh.first + c;
       QuotientArgs qa = qa0;
       for (int q = 0; q < 4; q++) qa.zh_inv[q] = cir.zh_inv[j];       // X^n - 1 = s_j^n - 1 on the whole coset
       hipLaunchKernelGGL(quotient_coset, dim3(blocks), dim3(256), 0, w->stream, ev + (size_t)c * 5 * n, sh.pre + (size_t)c * 9 * n, sh.xs + (size_t)c * n, n, qa, tq, 1u);
       BP_HIP(ctx, hipGetLastError());
-      rc = ntt_run(w, tq, k, 1, 1, n);
-      if (rc == BP_OK) rc = fr_binary_run(w, tq, n, sh.sinv + (size_t)c * n, n, tq, n, 2);      // coefficients of t mod (x^n - s_j^n)
-      if (rc != BP_OK) {
-        ctx->last_error = w->last_error;
-        return rc;
-      }
+      BP_TRY(lift(ctx, w, ntt_run(w, tq, k, 1, 1, n)));
+      BP_TRY(lift(ctx, w, fr_binary_run(w, tq, n, sh.sinv + (size_t)c * n, n, tq, n, 2)));      // coefficients of t mod (x^n - s_j^n)
       // back to the leader: the copy is issued on the work stream (it follows the kernels that produced tq)
       hipError_t he = !peer_path(sh.member ? sh.member : w, ctx->device)
                           ? hipMemcpyAsync(v + (size_t)j * n, tq, n * sizeof(fr_t), hipMemcpyDeviceToDevice, w->stream)
@@ -458,7 +340,7 @@ static int round3_by_coset(bp_ctx* ctx, const CircuitEntry& cir, const fr_t* con
   DeviceGuard guard(ctx->device);
   for (const CosetShare& sh : cir.split) BP_HIP(ctx, hipStreamWaitEvent(ctx->stream, sh.done, 0));
   RecombineArgs ra;
-  const fr_t quarter = finv(from_u64(4)), gn_inv = finv(gn);
+  const fr_t quarter = finv(fr_from_u64(4)), gn_inv = finv(gn);
   ra.scale[0] = quarter;
   for (int mm = 1; mm < 4; mm++) ra.scale[mm] = fmul(ra.scale[mm - 1], gn_inv);
   ra.iinv = finv(i4);
@@ -473,7 +355,7 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
               const ProveStaged* staged) {
   const uint32_t k = cir.log_n;
   const size_t n = (size_t)1 << k, N = 4 * n;
-  const fr_t omega = root_of_unity(n), k1 = from_u64(2), k2 = from_u64(3), one = Fr::one();      // prover.rs:99-100
+  const fr_t omega = root_of_unity(n), k1 = fr_from_u64(2), k2 = fr_from_u64(3), one = Fr::one();      // prover.rs:99-100
   hipStream_t st = ctx->stream;
   if (ctx->side) BP_HIP(ctx, stream_wait(ctx->side->stream));     // side work of a proof that was abandoned half way must not outlive its buffers
   for (const CosetShare& sh : cir.split) {
@@ -597,12 +479,8 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
     if (pi_zero) BP_HIP(ctx, hipMemsetAsync(ev + 4 * N, 0, N * sizeof(fr_t), ss));
     else hipLaunchKernelGGL(fr_mul_table_pad, dim3(blocks_N), dim3(256), 0, ss, coefs + 3 * n, n, cir.g_pow, ev + 4 * N, N);
     BP_HIP(ctx, hipGetLastError());
-    int rc = ntt_run(side, ev, k + 2, 0, 3, N);
-    if (rc == BP_OK && !pi_zero) rc = ntt_run(side, ev + 4 * N, k + 2, 0, 1, N);
-    if (rc != BP_OK) {
-      ctx->last_error = side->last_error;
-      return rc;
-    }
+    BP_TRY(lift(ctx, side, ntt_run(side, ev, k + 2, 0, 3, N)));
+    if (!pi_zero) BP_TRY(lift(ctx, side, ntt_run(side, ev + 4 * N, k + 2, 0, 1, N)));
     BP_HIP(ctx, hipEventRecord(ctx->side_ev[1], ss));
   }
   host_compress48_many(proof, &cm[0], 3);        // compressed once, into the proof; the transcript absorbs the same 48 bytes (transcript.rs:66-69)
@@ -700,9 +578,9 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
   const double t_r4 = now_ms();
 
   // ---- round 5 (prover.rs:543-647): linearisation r and the two opening quotients
-  const fr_t zeta_n = fpow(zeta, n), zh_zeta = fsub(zeta_n, one);
+  const fr_t zeta_n = fr_pow_u64(zeta, n), zh_zeta = fsub(zeta_n, one);
   // L1(zeta) = (1/n) sum_i zeta^i  (l1_coeff.coeffs_evaluate, :590)
-  const fr_t l1_zeta = big_eq(zeta, one) ? one : fmul(zh_zeta, finv(fmul(from_u64(n), fsub(zeta, one))));
+  const fr_t l1_zeta = big_eq(zeta, one) ? one : fmul(zh_zeta, finv(fmul(fr_from_u64(n), fsub(zeta, one))));
   const fr_t bz = fmul(beta, zeta);
   const fr_t f_a = fadd(fadd(a_bar, bz), gamma), f_b = fadd(fadd(b_bar, fmul(bz, k1)), gamma), f_c = fadd(fadd(c_bar, fmul(bz, k2)), gamma);
   const fr_t g_a = fadd(fadd(a_bar, fmul(s1_bar, beta)), gamma), g_b = fadd(fadd(b_bar, fmul(s2_bar, beta)), gamma);
@@ -766,7 +644,7 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
   // ---- Proof (verifier.rs:23-40 field order): 9 compressed points, then the 6 evaluations as 32-byte little-endian
   host_compress48_many(proof + 336, &cm[7], 2);                   // the first seven were compressed when the transcript absorbed them
   const fr_t evals[6] = {a_bar, b_bar, c_bar, s1_bar, s2_bar, zw_bar};
-  for (int j = 0; j < 6; j++) to_le32(proof + 432 + 32 * j, evals[j]);
+  for (int j = 0; j < 6; j++) fr_to_bytes(proof + 432 + 32 * j, evals[j], BP_FR_BYTES_LE);
   ctx->prove_ms[0] = (float)(t_r1 - t_start); ctx->prove_ms[1] = (float)(t_r2 - t_r1); ctx->prove_ms[2] = (float)(t_r3 - t_r2);
   ctx->prove_ms[3] = (float)(t_r4 - t_r3); ctx->prove_ms[4] = (float)(t_r5 - t_r4); ctx->prove_ms[5] = (float)(now_ms() - t_start);
   return BP_OK;

@@ -295,6 +295,22 @@ def test_rejections_name_the_lowest_proof_and_leave_the_output_alone(ctx):
     assert ctx.verify_reduce(3, vk, good[:624 * 2], None, weights[:2], fmt=FR_BYTES_LE) == good2
 
 
+def test_vk_record_of_zero_coordinates_is_the_identity_only_with_the_infinity_flag(ctx):
+    """a verifier-key commitment of 96 zero bytes is canonical and carries no flag, so it is the pair (0, 0), which is not on the curve:
+    BP_ERR_BAD_POINT, as G1Affine::from_uncompressed refuses it; the same slot as 0x40 and zeros is the identity and is taken"""
+    rnd = random.Random(78)
+    good = blob(dlog_records(rnd, 2))
+    vk, weights = vk_of([rnd.randrange(1, Q) for _ in range(8)]), scal([rnd.randrange(Q) for _ in range(2)], (2,))
+    for k in (0, 3, 7):
+        with pytest.raises(bp.BpError) as e:
+            ctx.verify_reduce(3, vk[:96 * k] + bytes(96) + vk[96 * (k + 1):], good, None, weights, fmt=FR_BYTES_LE)
+        assert e.value.code == -3 and ("commitment %d rejected" % k) in str(e.value)
+        a, b = ctx.verify_reduce(3, vk[:96 * k] + bytes([0x40]) + bytes(95) + vk[96 * (k + 1):], good, None, weights, fmt=FR_BYTES_LE)
+        assert len(a) == 96 and len(b) == 96
+    a, b = ctx.verify_reduce(3, vk, good, None, weights, fmt=FR_BYTES_LE)          # no stale error: the valid key still goes through
+    assert len(a) == 96 and len(b) == 96
+
+
 def test_stage_times_are_sane_and_group_contexts_use_their_primary(ctx):
     rnd = random.Random(3)
     m = 2048

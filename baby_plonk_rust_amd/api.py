@@ -295,6 +295,15 @@ class Context:
         return {"accumulate_ms": a.value, "device_ms": t.value, "mixed_adds": adds.value, "window_bits": c.value,
                 "tables": self._lib.bp_msm_last_used_tables(self._h) == 1}
 
+    MSM_PATH_FIELDS = ("J", "c", "W", "radix", "sort", "pb", "packed", "flat", "wide8", "fixup", "n_wide", "chunk")
+
+    def msm_path(self, member=0):
+        """which path the last MSM pipeline on a member's context took (bp_msm_last_path): J vectors, c, W, radix, sort (1 two-level,
+        2 partition), pb, packed, flat, wide8, fixup (0 per bucket, 1 per edge), n_wide, chunk"""
+        out = (C.c_uint32 * 12)()
+        self.check(self._lib.bp_msm_last_path(self._h, member, out), "bp_msm_last_path")
+        return dict(zip(self.MSM_PATH_FIELDS, (int(v) for v in out)))
+
     def msm_member_stats(self):
         """per member of a group context: upload (host scalars only), accumulate and whole-pipeline device times of the last MSM"""
         out = []

@@ -560,6 +560,13 @@ int bp_msm_last_member_stats(bp_ctx* ctx, int member, float* upload_ms, float* a
   if (mixed_adds) *mixed_adds = group ? m->shard_adds : m->msm_adds;
   return BP_OK;
 }
+int bp_msm_last_path(bp_ctx* ctx, int member, uint32_t out[12]) {
+  if (!ctx || !out) return BP_ERR_INVALID_ARG;
+  const std::vector<bp_ctx*> sh = shards_of(ctx);
+  if (member < 0 || (size_t)member >= sh.size()) return BP_ERR_INVALID_ARG;
+  memcpy(out, sh[member]->msm_path, sizeof sh[member]->msm_path);
+  return BP_OK;
+}
 int bp_msm_last_used_tables(bp_ctx* ctx) { return ctx ? (ctx->msm_tables ? 1 : 0) : BP_ERR_INVALID_ARG; }
 int bp_msm_last_stats(bp_ctx* ctx, float* accumulate_ms, float* total_device_ms, uint64_t* mixed_adds, uint32_t* window_bits) {
   if (!ctx) return BP_ERR_INVALID_ARG;

@@ -152,6 +152,9 @@ struct bp_ctx {
   uint64_t msm_adds = 0;
   uint32_t msm_c = 0;
   bool msm_tables = false;
+  // what the last msm_launch_many that enqueued a pipeline on THIS context decided (bp_msm_last_path): J, c, W, radix, sort (1 two-level,
+  // 2 partition; 0 the experiment build's counting sort), pb, packed, flat, wide8, fixup (0 per bucket, 1 per edge), n_wide, chunk
+  uint32_t msm_path[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float prove_ms[6] = {0, 0, 0, 0, 0, 0};            // host wall clock of rounds 1..5 and of the whole bp_prove
   bool msm_async_pending = false;  // bp_msm_g1_blob_device_async enqueued an MSM whose events have not been read yet
   float ntt_ms = 0;

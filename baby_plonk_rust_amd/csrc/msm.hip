@@ -359,6 +359,8 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   const int sort_mode = (EXPERIMENT_BUILD && sort_env == 0 && hist_ok) ? 0 : ((((sort_env == 1 || sort_env == 3) && J == 1) || pb > PART_MAX_BITS) ? 1 : 2);
   if (sort_mode != 2 && J > 1) return fail(ctx, BP_ERR_TOO_LARGE, "MSM batch too long for the partition sort", hipSuccess, __FILE__, __LINE__);
   const uint32_t rbits = kb - pb, n_final = 1u << pb;
+  // what this launch decided (bp_msm_last_path): host words only, copied into the context once everything is enqueued
+  uint32_t path[12] = {J, plan.c, W, plan.radix, (uint32_t)sort_mode, pb, 0u, 0u, 0u, 0u, 0u, plan.chunk};
   const size_t rhist = ((size_t)1 << rbits) * 4;
   BP_HIP(ctx, hipMemsetAsync(ctl, 0, (ctl_fixed + n_final) * 4, st));
   uint32_t* rlong_n = ctl + 2;
@@ -396,6 +398,9 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     const uint32_t flat_env = knob_u32("BP_MSM_PART_FLAT", 2, 0, 2);
     const bool flat = wide8 ? false : (flat_env == 2 ? (cap >> pb) < 8 : flat_env == 1);
     const size_t part_lds = (size_t)3 * n_final * 4 + (size_t)cap * rec_bytes + (flat ? (size_t)cap * 2 : 0);
+    path[6] = packed;
+    path[7] = flat;
+    path[8] = wide8;
     const dim3 lgrid(64, n_final < 4 ? n_final : 4);
     // short final runs (2^12 runs of ~3 Ki records at c = 20): 512-lane workgroups (measured 70 / 60 / 72 us at 256 / 512 / 1024 lanes)
     const unsigned final_threads = knob_u32("BP_MSM_FINAL_THREADS", (max_entries >> pb) <= 8192 ? 512 : 1024, 256, 1024) & ~63u;
@@ -547,6 +552,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   // sit inside one chunk -- one lane per chunk edge.  BP_MSM_FIXUP=1 / 2 forces the per-bucket / per-edge form.
   const uint32_t fixup_env = knob_u32("BP_MSM_FIXUP", 0, 0, 2);
   const bool by_edges = fixup_env ? fixup_env == 2 : max_entries / total < 2ull * plan.chunk;
+  path[9] = by_edges;
   if (by_edges)
     hipLaunchKernelGGL(msm_fixup_edges, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count,
                        long_list, long_cap);
@@ -573,6 +579,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     // a lone wide leaf level (two-level trees, c = 3: knobs only) takes the step path in the shipped library -- its single-level LEAF kernel
     // is the one tree kernel that spills (tools/kernel_resources.py) and lives in the experiment build only (BP_MSM_PLANES_FUSE01=0)
     if (!EXPERIMENT_BUILD && n_wide < 2) n_wide = 0;
+    path[10] = n_wide;
     proj28_slot* tmp[2] = {nullptr, nullptr};
     {
       size_t need[2] = {0, 0};
@@ -661,6 +668,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   out->quads = quads;
   out->adds = max_entries;      // upper bound (blob mode keeps it); msm_finish replaces it by the exact count of non-zero digits
   out->h_windows = h_windows;
+  memcpy(ctx->msm_path, path, sizeof path);
   return BP_OK;
 }
 

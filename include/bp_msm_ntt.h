@@ -233,6 +233,12 @@ int  bp_msm_last_stats(bp_ctx* ctx, float* accumulate_ms, float* total_device_ms
  * Setup::commit(&Polynomial) (setup.rs:32-37) over the GPUs into PCIe time and compute time.  Any pointer may be null. */
 int  bp_msm_last_member_stats(bp_ctx* ctx, int member, float* upload_ms, float* accumulate_ms, float* total_device_ms,
                               uint64_t* mixed_adds);
+/* Which path the last MSM pipeline enqueued on a member's context took (member as in bp_msm_last_member_stats), twelve words:
+ * J (scalar vectors in the pipeline), c, W (windows), radix (live buckets of a radix-R width, else 0), sort (1 two-level, 2 partition),
+ * pb (partition bits), packed (one-word records), flat (flat write-out), wide8 (1 024-scalar slices of two-word records), fixup
+ * (0 per bucket, 1 per chunk edge), n_wide (tree levels run one addition per lane), chunk (entries per accumulation lane).  Host
+ * words stored at launch time: nothing is timed, waited for or read from the device; an empty MSM launches nothing and leaves them. */
+int  bp_msm_last_path(bp_ctx* ctx, int member, uint32_t out[12]);
 /* 1 when the last MSM on this ctx went through fixed-base tables, 0 when not, negative on error. */
 int  bp_msm_last_used_tables(bp_ctx* ctx);
 

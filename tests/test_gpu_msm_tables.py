@@ -204,6 +204,8 @@ def test_full_size_2p24_closed_form_both_paths(ctx):
     assert info["window_bits"] == 22 and info["windows"] == 12 and info["bytes"] == 12 * n * 128
     assert bp.sum_partials(ctx.msm_partial(h, None, device_ptr=t.data_ptr(), n=n)) == want and ctx.msm_stats()["tables"]
     assert ctx.msm_stats()["window_bits"] == 22
+    path = ctx.msm_path()                                            # 12 * 2^24 entries: beyond the partition sort's 2^12 final runs
+    assert (path["J"], path["c"], path["W"], path["sort"], path["fixup"]) == (1, 22, 12, 1, 1)
     info = ctx.srs_precompute(h, 20)                                 # the width of 2^20 .. 2^23 points
     assert info["window_bits"] == 20 and info["windows"] == 13 and info["bytes"] == 13 * n * 128
     assert bp.sum_partials(ctx.msm_partial(h, None, device_ptr=t.data_ptr(), n=n)) == want and ctx.msm_stats()["window_bits"] == 20

@@ -431,9 +431,10 @@ def test_commit_many_device():
     for ctx in (bp.Context(0), bp.Context([0, 0, 0])):
         n = 5000
         setup = bp.Setup.generate_srs(n, 0xABCDEF, ctx)
-        polys = [bp.DevicePolynomial(O.splitmix_scalars(m, 0xC0 + m), bp.BASIS_MONOMIAL, ctx) for m in (n, n - 6, 17, n + 9, 1)]
+        polys = [bp.DevicePolynomial(O.splitmix_scalars(m, 0xC0 + m), bp.BASIS_MONOMIAL, ctx) for m in (n, n - 6, 0, 17, n + 9, 1)]
         one_by_one = [bp.commit_device(setup, p) for p in polys]
         assert bp.commit_many_device(setup, polys) == one_by_one
+        assert one_by_one[2] == M.enc96(None)                         # the empty polynomial: the identity
         assert bp.commit_many_device(setup, polys[:1]) == one_by_one[:1] and bp.commit_many_device(setup, []) == []
         with pytest.raises(bp.BpError):
             bp.commit_many_device(setup, [bp.DevicePolynomial(O.splitmix_scalars(8, 1), bp.BASIS_LAGRANGE, ctx)])

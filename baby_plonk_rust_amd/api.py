@@ -509,8 +509,63 @@ class BucketMSM:
             ctx.srs_free(h)
 
 
-class Polynomial:
+class _PolynomialOps:
+    """The operators Polynomial and DevicePolynomial share (polynomial.rs:34-380, utils.rs:170-175).  A subclass says where its values
+    live: _SUFFIX and _FMT (the suffix of its entry points' names and their scalar_fmt argument, if they take one), _ptr(),
+    _alloc(n) -- a new polynomial of the same basis and context with room for n values -- and _cut(n), which keeps the first n."""
+
+    def _same_kind(self, other):         # a Polynomial with a Polynomial, a DevicePolynomial with a DevicePolynomial (subclasses included)
+        return isinstance(other, _PolynomialOps) and other._SUFFIX == self._SUFFIX
+
+    def _call(self, name, fn, *args):
+        c = self.ctx
+        c.check(getattr(c._lib, fn + self._SUFFIX)(c._h, self._ptr(), len(self), *args), name)
+
+    def _binop(self, other, fn, name, out_len):
+        if self.basis != other.basis:
+            raise BpError(-5, name, "Basis must be the same")
+        out, n = self._alloc(out_len), C.c_size_t()
+        self._call(name, fn, other._ptr(), len(other), self.basis, *self._FMT, out._ptr(), C.byref(n))
+        out._cut(n.value)
+        return out
+
+    def _scalar(self, s, op, name):
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
+        out = self._alloc(len(self))
+        self._call(name, "bp_poly_scalar_op", self.basis, s.ctypes.data, op, *self._FMT, out._ptr())
+        return out
+
+    def __add__(self, other):            # polynomial.rs:57-117
+        if self._same_kind(other):
+            return self._binop(other, "bp_poly_add", "Polynomial + Polynomial", max(len(self), len(other)))
+        return self._scalar(other, 0, "Polynomial + Scalar")
+
+    def __sub__(self, other):            # polynomial.rs:119-174
+        if self._same_kind(other):
+            return self._binop(other, "bp_poly_sub", "Polynomial - Polynomial", max(len(self), len(other)))
+        return self._scalar(other, 1, "Polynomial - Scalar")
+
+    def __mul__(self, other):            # polynomial.rs:176-312
+        if self._same_kind(other):
+            return self._binop(other, "bp_poly_mul", "Polynomial * Polynomial", len(self) + len(other))
+        return self._scalar(other, 2, "Polynomial * Scalar")
+
+    def __truediv__(self, other):        # polynomial.rs:314-380
+        return self._binop(other, "bp_poly_div", "Polynomial / Polynomial", max(len(self), 1))
+
+    def rlc(self, other, beta, gamma):   # impl Rlc for Polynomial (utils.rs:170-175): self + other * beta + gamma
+        return self + other * beta + gamma
+
+    def coeffs_evaluate(self, x):        # polynomial.rs:34-45
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+        out = np.zeros(4, dtype=np.uint64)
+        self._call("coeffs_evaluate", "bp_poly_evaluate", self.basis, x.ctypes.data, *self._FMT, out.ctypes.data)
+        return out
+
+
+class Polynomial(_PolynomialOps):
     """polynomial.rs:14-17; value semantics (every operator returns a new object)"""
+    _SUFFIX, _FMT = "", (FR_MONT,)
 
     def __init__(self, values, basis, ctx=None):
         self.values = _fr_array(values).copy() if len(values) else np.zeros((0, 4), dtype=np.uint64)
@@ -524,52 +579,16 @@ class Polynomial:
     def __eq__(self, other):
         return self.basis == other.basis and self.values.shape == other.values.shape and bool((self.values == other.values).all())
 
-    def _binop(self, other, fn, name):
-        if self.basis != other.basis:
-            raise BpError(-5, name, "Basis must be the same")
-        out = np.zeros((max(len(self) + len(other), 1), 4), dtype=np.uint64)
-        n = C.c_size_t()
-        c = self.ctx
-        c.check(fn(c._h, self.values.ctypes.data, len(self), other.values.ctypes.data, len(other), self.basis, FR_MONT,
-                   out.ctypes.data, C.byref(n)), name)
-        return Polynomial(out[: n.value], self.basis, c)
+    def _ptr(self):
+        return self.values.ctypes.data
 
-    def _scalar(self, s, op, name):
-        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
-        out = np.zeros_like(self.values)
-        c = self.ctx
-        c.check(c._lib.bp_poly_scalar_op(c._h, self.values.ctypes.data, len(self), self.basis, s.ctypes.data, op, FR_MONT,
-                                         out.ctypes.data), name)
-        return Polynomial(out, self.basis, c)
-
-    def __add__(self, other):            # polynomial.rs:57-117
-        if isinstance(other, Polynomial):
-            return self._binop(other, self.ctx._lib.bp_poly_add, "Polynomial + Polynomial")
-        return self._scalar(other, 0, "Polynomial + Scalar")
-
-    def __sub__(self, other):            # polynomial.rs:119-174
-        if isinstance(other, Polynomial):
-            return self._binop(other, self.ctx._lib.bp_poly_sub, "Polynomial - Polynomial")
-        return self._scalar(other, 1, "Polynomial - Scalar")
-
-    def __mul__(self, other):            # polynomial.rs:176-312
-        if isinstance(other, Polynomial):
-            return self._binop(other, self.ctx._lib.bp_poly_mul, "Polynomial * Polynomial")
-        return self._scalar(other, 2, "Polynomial * Scalar")
-
-    def __truediv__(self, other):        # polynomial.rs:314-380
-        return self._binop(other, self.ctx._lib.bp_poly_div, "Polynomial / Polynomial")
-
-    def rlc(self, other, beta, gamma):   # impl Rlc for Polynomial (utils.rs:170-175): self + other * beta + gamma
-        return self + other * beta + gamma
-
-    def coeffs_evaluate(self, x):        # polynomial.rs:34-45
-        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
-        out = np.zeros(4, dtype=np.uint64)
-        c = self.ctx
-        c.check(c._lib.bp_poly_evaluate(c._h, self.values.ctypes.data, len(self), self.basis, x.ctypes.data, FR_MONT,
-                                        out.ctypes.data), "coeffs_evaluate")
+    def _alloc(self, n):
+        out = Polynomial((), self.basis, self.ctx)
+        out.values = np.zeros((max(n, 1), 4), dtype=np.uint64)[:n]
         return out
+
+    def _cut(self, n):
+        self.values = self.values[:n]
 
     def ntt(self):                       # polynomial.rs:47-51
         if self.basis != BASIS_MONOMIAL:
@@ -587,9 +606,10 @@ class Polynomial:
         return np.roll(self.values, -(n % len(self)), axis=0)
 
 
-class DevicePolynomial:
+class DevicePolynomial(_PolynomialOps):
     """polynomial.rs:14-17 with the coefficient / value vector resident in HBM (torch CUDA tensor, int64 [n, 4] =
     Montgomery limbs).  Same operators and rules as Polynomial; nothing but O(1) scalars crosses PCIe."""
+    _SUFFIX, _FMT = "_device", ()
 
     def __init__(self, values, basis, ctx=None):
         import torch
@@ -618,50 +638,11 @@ class DevicePolynomial:
     def _ptr(self):
         return self.t.data_ptr() if len(self) else 0
 
-    def _binop(self, other, fn, name, out_len):
-        if self.basis != other.basis:
-            raise BpError(-5, name, "Basis must be the same")
-        out = DevicePolynomial.empty(out_len, self.basis, self.ctx)
-        n = C.c_size_t()
-        c = self.ctx
-        c.check(fn(c._h, self._ptr(), len(self), other._ptr(), len(other), self.basis, out._ptr(), C.byref(n)), name)
-        out.t = out.t[: n.value]
-        return out
+    def _alloc(self, n):
+        return DevicePolynomial.empty(n, self.basis, self.ctx)
 
-    def _scalar(self, s, op, name):
-        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
-        out = DevicePolynomial.empty(len(self), self.basis, self.ctx)
-        c = self.ctx
-        c.check(c._lib.bp_poly_scalar_op_device(c._h, self._ptr(), len(self), self.basis, s.ctypes.data, op, out._ptr()), name)
-        return out
-
-    def __add__(self, o):
-        if isinstance(o, DevicePolynomial):
-            return self._binop(o, self.ctx._lib.bp_poly_add_device, "Polynomial + Polynomial", max(len(self), len(o)))
-        return self._scalar(o, 0, "Polynomial + Scalar")
-
-    def __sub__(self, o):
-        if isinstance(o, DevicePolynomial):
-            return self._binop(o, self.ctx._lib.bp_poly_sub_device, "Polynomial - Polynomial", max(len(self), len(o)))
-        return self._scalar(o, 1, "Polynomial - Scalar")
-
-    def __mul__(self, o):
-        if isinstance(o, DevicePolynomial):
-            return self._binop(o, self.ctx._lib.bp_poly_mul_device, "Polynomial * Polynomial", len(self) + len(o))
-        return self._scalar(o, 2, "Polynomial * Scalar")
-
-    def __truediv__(self, o):
-        return self._binop(o, self.ctx._lib.bp_poly_div_device, "Polynomial / Polynomial", max(len(self), 1))
-
-    def rlc(self, other, beta, gamma):   # impl Rlc for Polynomial (utils.rs:170-175)
-        return self + other * beta + gamma
-
-    def coeffs_evaluate(self, x):
-        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
-        out = np.zeros(4, dtype=np.uint64)
-        c = self.ctx
-        c.check(c._lib.bp_poly_evaluate_device(c._h, self._ptr(), len(self), self.basis, x.ctypes.data, out.ctypes.data), "coeffs_evaluate")
-        return out
+    def _cut(self, n):
+        self.t = self.t[:n]
 
     def _transform(self, inverse, need, to):
         if self.basis != need:

@@ -180,14 +180,14 @@ static int comm_agree(bp_ctx* ctx, uint32_t tag, int local_rc, uint64_t a, uint6
       char buf[200];
       snprintf(buf, sizeof buf, "%s: rank %zu failed before the collective (code %d); every rank returns it", what, r, (int)h[1 + r].rc);
       const int code = h[1 + r].rc < 0 && h[1 + r].rc >= BP_ERR_COMM ? h[1 + r].rc : BP_ERR_INVALID_ARG;
-      return fail(ctx, code, buf, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, code, buf);
     }
   for (size_t r = 0; r < world; r++)
     if (h[1 + r].tag != tag || h[1 + r].a != a || h[1 + r].b != b || h[1 + r].c != c) {
       char buf[200];
       snprintf(buf, sizeof buf, "%s: rank %zu joined with other arguments (%llu, %llu against %llu, %llu here)", what, r,
                (unsigned long long)h[1 + r].a, (unsigned long long)h[1 + r].b, (unsigned long long)a, (unsigned long long)b);
-      return fail(ctx, BP_ERR_INVALID_ARG, buf, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, BP_ERR_INVALID_ARG, buf);
     }
   return BP_OK;
 }
@@ -229,9 +229,9 @@ struct InitJob {
 
 int bp_comm_init_rank(bp_ctx* ctx, const uint8_t id[BP_COMM_ID_BYTES], int rank, int world) {
   if (!ctx || !id || world < 1 || rank < 0 || rank >= world) return BP_ERR_INVALID_ARG;
-  if (is_group(ctx)) return fail(ctx, BP_ERR_INVALID_ARG, "a bp_init_multi context combines its shards itself; communicators belong to plain (one GPU) contexts", hipSuccess, __FILE__, __LINE__);
-  if (ctx->comm) return fail(ctx, BP_ERR_INVALID_ARG, "this context already has a communicator (bp_comm_destroy first)", hipSuccess, __FILE__, __LINE__);
-  if (ctx->comm_init_stuck) return fail(ctx, BP_ERR_COMM, "an earlier bp_comm_init_rank of this context ran into its bound and is still inside RCCL; use a fresh context (or process)", hipSuccess, __FILE__, __LINE__);
+  if (is_group(ctx)) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "a bp_init_multi context combines its shards itself; communicators belong to plain (one GPU) contexts");
+  if (ctx->comm) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "this context already has a communicator (bp_comm_destroy first)");
+  if (ctx->comm_init_stuck) return BP_FAIL(ctx, BP_ERR_COMM, "an earlier bp_comm_init_rank of this context ran into its bound and is still inside RCCL; use a fresh context (or process)");
   DeviceGuard guard(ctx->device);
   // everything a collective will need, BEFORE the communicator exists: a failure here is a plain local error, no peer is involved yet
   comm_release(ctx);
@@ -267,7 +267,7 @@ int bp_comm_init_rank(bp_ctx* ctx, const uint8_t id[BP_COMM_ID_BYTES], int rank,
       char buf[256];
       snprintf(buf, sizeof buf, "ncclCommInitRank(rank %d of %d) did not return within %u ms (bp_comm_set_timeout_ms): a rank never called "
                "bp_comm_init_rank with this id", rank, world, bound_ms);
-      return fail(ctx, BP_ERR_COMM, buf, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, BP_ERR_COMM, buf);
     }
   }
   helper.join();
@@ -311,14 +311,14 @@ int bp_comm_destroy(bp_ctx* ctx) {
 int bp_msm_g1_allgather(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
                         int scalars_on_device, uint8_t out96[96]) {
   if (!ctx) return BP_ERR_INVALID_ARG;
-  if (!ctx->comm) return fail(ctx, BP_ERR_INVALID_ARG, "no communicator on this context (bp_comm_init_rank)", hipSuccess, __FILE__, __LINE__);
+  if (!ctx->comm) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "no communicator on this context (bp_comm_init_rank)");
   const size_t world = (size_t)ctx->comm_world;
   DeviceGuard guard(ctx->device);
   uint8_t *mine = dev_mine(ctx), *gathered = dev_gathered(ctx), *summed = dev_summed(ctx);
   hipStream_t st = ctx->stream;
   // This rank's record.  From here to the all-gather NOTHING returns: whatever goes wrong locally becomes a poisoned record.
   int local = (!out96 || !fmt_ok(scalar_fmt) || (n_scalars && !scalars)) ? BP_ERR_INVALID_ARG : BP_OK;
-  if (local != BP_OK) (void)fail(ctx, local, "bp_msm_g1_allgather: null pointer or bad scalar format", hipSuccess, __FILE__, __LINE__);
+  if (local != BP_OK) (void)BP_FAIL(ctx, local, "bp_msm_g1_allgather: null pointer or bad scalar format");
   if (local == BP_OK) local = bp_msm_g1_blob_device_async(ctx, srs_handle, first, scalars, n_scalars, scalar_fmt, scalars_on_device, mine);
   std::string local_text;
   if (local != BP_OK) {
@@ -344,7 +344,7 @@ int bp_msm_g1_allgather(bp_ctx* ctx, uint64_t srs_handle, size_t first, const vo
   if (rc != 0) {
     char buf[200];
     snprintf(buf, sizeof buf, "bp_msm_g1_allgather: rank %u failed before the collective (code %d); every rank returns it", bad_rank, rc);
-    return fail(ctx, rc, buf, hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, rc, buf);
   }
   g1_proj r;
   uint32_t magic;
@@ -356,8 +356,8 @@ int bp_msm_g1_allgather(bp_ctx* ctx, uint64_t srs_handle, size_t first, const vo
     BP_TRY(comm_stream_wait(ctx, "bp_msm_g1_allgather", __LINE__));
     rc = msm_blobs_combine((const uint8_t*)ctx->comm_host, world, &r);
   }
-  if (rc == BP_ERR_BAD_SCALAR) return fail(ctx, rc, "scalar >= q in a canonical-bytes input (on some rank)", hipSuccess, __FILE__, __LINE__);
-  if (rc != BP_OK) return fail(ctx, rc, "gathered MSM records", hipSuccess, __FILE__, __LINE__);
+  if (rc == BP_ERR_BAD_SCALAR) return BP_FAIL(ctx, rc, "scalar >= q in a canonical-bytes input (on some rank)");
+  if (rc != BP_OK) return BP_FAIL(ctx, rc, "gathered MSM records");
   host_encode96(out96, r);
   return BP_OK;
 }
@@ -374,15 +374,15 @@ int bp_comm_last_exchange_ms(bp_ctx* ctx, float* ms) {
 // context's stream, waited for under the bound.
 int bp_ntt_columns_allgather(bp_ctx* ctx, void* d_columns, uint32_t log_n, size_t columns_per_rank) {
   if (!ctx) return BP_ERR_INVALID_ARG;
-  if (!ctx->comm) return fail(ctx, BP_ERR_INVALID_ARG, "no communicator on this context (bp_comm_init_rank)", hipSuccess, __FILE__, __LINE__);
+  if (!ctx->comm) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "no communicator on this context (bp_comm_init_rank)");
   DeviceGuard guard(ctx->device);
   int local = BP_OK;
   size_t block = 0, all = 0;
-  if (!d_columns && columns_per_rank) local = fail(ctx, BP_ERR_INVALID_ARG, "bp_ntt_columns_allgather: null column buffer", hipSuccess, __FILE__, __LINE__);
-  else if (log_n > 28) local = fail(ctx, BP_ERR_TOO_LARGE, "bp_ntt_columns_allgather: columns longer than 2^28 elements", hipSuccess, __FILE__, __LINE__);
+  if (!d_columns && columns_per_rank) local = BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_ntt_columns_allgather: null column buffer");
+  else if (log_n > 28) local = BP_FAIL(ctx, BP_ERR_TOO_LARGE, "bp_ntt_columns_allgather: columns longer than 2^28 elements");
   else if (__builtin_mul_overflow(columns_per_rank, ((size_t)1 << log_n) * sizeof(fr_t), &block) ||
            __builtin_mul_overflow(block, (size_t)ctx->comm_world, &all))
-    local = fail(ctx, BP_ERR_TOO_LARGE, "bp_ntt_columns_allgather: columns_per_rank * world * 2^log_n * 32 overflows", hipSuccess, __FILE__, __LINE__);
+    local = BP_FAIL(ctx, BP_ERR_TOO_LARGE, "bp_ntt_columns_allgather: columns_per_rank * world * 2^log_n * 32 overflows");
   // the ranks' statuses and shapes first: a rank that cannot take part says so INSIDE a collective instead of staying away from one
   BP_TRY(comm_agree(ctx, AGREE_COLUMNS, local, log_n, columns_per_rank, 0, "bp_ntt_columns_allgather"));
   if (block == 0) return BP_OK;

@@ -98,7 +98,7 @@ int download_fr(bp_ctx* ctx, fr_t* d, void* host, size_t n, int fmt, const uint3
   if (n) BP_HIP(ctx, hipMemcpyAsync(host, d, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
   if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
-  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);
+  if (bad) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "vector element >= q");
   return BP_OK;
 }
 
@@ -245,7 +245,7 @@ int side_ctx_get(bp_ctx* ctx, bp_ctx** out) {
   if (!ctx->side) {
     bp_ctx* sd = nullptr;
     int rc = ctx_create(&sd, ctx->device);
-    if (rc != BP_OK) return fail(ctx, rc, "side context", hipSuccess, __FILE__, __LINE__);
+    if (rc != BP_OK) return BP_FAIL(ctx, rc, "side context");
     ctx->side = sd;
     DeviceGuard guard(ctx->device);
     for (auto& e : ctx->side_ev)

@@ -48,7 +48,7 @@ static int msm_all_shards_launch(bp_ctx* ctx, uint64_t srs_handle, size_t first,
                                  int scalars_on_device, int slot, ShardedPending* sp) {
   std::vector<SrsShard> sh;
   BP_TRY(srs_shards(ctx, srs_handle, &sh, first, n_scalars));            // more scalars than points: cut to the SRS (zip() truncation, msm.rs:29)
-  if (first > sh[0].e->n_global) return fail(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds", hipSuccess, __FILE__, __LINE__);
+  if (first > sh[0].e->n_global) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds");
   if (sh.size() > 1 && scalars_on_device) {            // the members' copies must see what the leader's stream has produced
     DeviceGuard guard(ctx->device);
     BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
@@ -225,7 +225,7 @@ static int lane_get(bp_ctx* ctx, int j, bp_ctx** out) {
   while ((int)ctx->lanes.size() < j) {
     bp_ctx* lane = nullptr;
     int rc = ctx_create(&lane, ctx->device);
-    if (rc != BP_OK) return fail(ctx, rc, "commit lane", hipSuccess, __FILE__, __LINE__);
+    if (rc != BP_OK) return BP_FAIL(ctx, rc, "commit lane");
     ctx->lanes.push_back(lane);
   }
   *out = lane_of(ctx, j);
@@ -324,7 +324,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
 
 int commit_lane_launch(bp_ctx* ctx, int j, uint64_t srs_handle, const fr_t* d_coeffs, size_t n, hipEvent_t ready, MsmPending* pend) {
   *pend = MsmPending();
-  if (j < 0 || j >= MAX_LANES || is_group(ctx)) return fail(ctx, BP_ERR_INVALID_ARG, "commit lane", hipSuccess, __FILE__, __LINE__);
+  if (j < 0 || j >= MAX_LANES || is_group(ctx)) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "commit lane");
   SrsEntry* e;
   BP_TRY(srs_find(ctx, srs_handle, &e));
   DeviceGuard guard(ctx->device);
@@ -451,10 +451,10 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
 static int msm_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
                            int scalars_on_device, void* d_blob, bool wait) {
   if (!ctx || !d_blob || !fmt_ok(scalar_fmt) || (n_scalars && !scalars)) return BP_ERR_INVALID_ARG;
-  if (is_group(ctx)) return fail(ctx, BP_ERR_INVALID_ARG, "blob records are the one-process-per-GPU exchange; a bp_init_multi context combines its shards itself", hipSuccess, __FILE__, __LINE__);
+  if (is_group(ctx)) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "blob records are the one-process-per-GPU exchange; a bp_init_multi context combines its shards itself");
   SrsEntry* e;
   BP_TRY(srs_find(ctx, srs_handle, &e));
-  if (first > e->n) return fail(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds", hipSuccess, __FILE__, __LINE__);
+  if (first > e->n) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds");
   const size_t n = std::min(n_scalars, e->n - first);
   DeviceGuard guard(ctx->device);
   MsmPending pend;

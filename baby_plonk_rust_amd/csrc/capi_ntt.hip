@@ -1,19 +1,15 @@
 // capi_ntt.hip -- C ABI, part 3: ntt_381 / i_ntt_381 (utils.rs:63-129), host and device forms, columns and one large transform over
 // the members of a group context, roots of unity, scalar format conversion.
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
 #include <functional>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "ctx.hpp"
 
 #include "capi_common.hpp"
+#include "poly_rules.hpp"
 
 using namespace bp;
 // ---------------------------------------------------------------------------------------------- DFT
@@ -175,11 +171,11 @@ static int ntt_one_over_members(bp_ctx* ctx, uint8_t* data, uint32_t log_n, int 
 
 int bp_ntt_fr(bp_ctx* ctx, void* data, uint32_t log_n, int inverse, int scalar_fmt, size_t batch, size_t stride) {
   if (!ctx || !fmt_ok(scalar_fmt) || (!data && batch)) return BP_ERR_INVALID_ARG;
-  if (log_n > 28) return fail(ctx, BP_ERR_TOO_LARGE, "NTT length > 2^28", hipSuccess, __FILE__, __LINE__);
+  if (log_n > 28) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "NTT length > 2^28");
   if (batch == 0) return BP_OK;
   const size_t N = (size_t)1 << log_n;
-  if (batch > 1 && stride < N) return fail(ctx, BP_ERR_INVALID_ARG, "NTT stride < N", hipSuccess, __FILE__, __LINE__);
-  if (batch > 65535) return fail(ctx, BP_ERR_TOO_LARGE, "NTT batch > 65535", hipSuccess, __FILE__, __LINE__);
+  if (batch > 1 && stride < N) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NTT stride < N");
+  if (batch > 65535) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "NTT batch > 65535");
   if (is_group(ctx) && batch > 1) return ntt_columns_over_members(ctx, (uint8_t*)data, log_n, inverse, scalar_fmt, batch, stride);
   if (is_group(ctx) && log_n >= knob_u32("BP_NTT_GROUP_SPLIT_FROM", 22, 11, 29)) {     // one large transform: every member's PCIe link and a share of the work
     const int rc = ntt_one_over_members(ctx, (uint8_t*)data, log_n, inverse, scalar_fmt);
@@ -229,17 +225,22 @@ int bp_root_of_unity(uint64_t group_order, int scalar_fmt, uint8_t out32[32]) {
   fr_to_bytes(out32, w, scalar_fmt);
   return BP_OK;
 }
-int bp_roots_of_unity(bp_ctx* ctx, uint64_t group_order, int scalar_fmt, void* out) {
+// roots_of_unity(group_order) into host memory in scalar_fmt, or (device) into HBM as Montgomery limbs
+static int roots_of_unity(bp_ctx* ctx, uint64_t group_order, bool device, int scalar_fmt, void* out) {
   if (!ctx || !out || !fmt_ok(scalar_fmt)) return BP_ERR_INVALID_ARG;
+  BP_RULE(ctx, rule_roots(group_order));
   fr_t w;
-  if (!host_root_of_unity(w, group_order)) return fail(ctx, BP_ERR_INVALID_ARG, "group_order == 0", hipSuccess, __FILE__, __LINE__);
-  if (group_order > ((uint64_t)1 << 28)) return fail(ctx, BP_ERR_TOO_LARGE, "group_order > 2^28", hipSuccess, __FILE__, __LINE__);
+  host_root_of_unity(w, group_order);
   DeviceGuard guard(ctx->device);
-  fr_t* d;
-  BP_TRY(ws_get(ctx, "io.roots", group_order * sizeof(fr_t), (void**)&d));
+  fr_t* d = (fr_t*)out;
+  if (!device) BP_TRY(ws_get(ctx, "io.roots", group_order * sizeof(fr_t), (void**)&d));
   BP_TRY(roots_run(ctx, w, group_order, d));
-  return download_fr(ctx, d, out, group_order, scalar_fmt);
+  if (!device) return download_fr(ctx, d, out, group_order, scalar_fmt);
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  return BP_OK;
 }
+int bp_roots_of_unity(bp_ctx* ctx, uint64_t group_order, int scalar_fmt, void* out) { return roots_of_unity(ctx, group_order, false, scalar_fmt, out); }
+int bp_roots_of_unity_device(bp_ctx* ctx, uint64_t group_order, void* d_out) { return roots_of_unity(ctx, group_order, true, BP_FR_MONT, d_out); }
 
 int bp_fr_convert(const void* in, size_t n, int from_fmt, int to_fmt, void* out) {
   if (!fmt_ok(from_fmt) || !fmt_ok(to_fmt) || (n && (!in || !out))) return BP_ERR_INVALID_ARG;

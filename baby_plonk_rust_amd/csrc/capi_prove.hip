@@ -18,8 +18,8 @@ using namespace bp;
 // ---------------------------------------------------------------------------------------------- prover
 int bp_circuit_load(bp_ctx* ctx, uint32_t log_n, const void* const columns[8], int scalar_fmt, int columns_on_device, uint64_t* handle) {
   if (!ctx || !columns || !handle || !fmt_ok(scalar_fmt)) return BP_ERR_INVALID_ARG;
-  if (log_n < 3 || log_n > 24) return fail(ctx, BP_ERR_INVALID_ARG, "circuit: log_n must be in 3..24", hipSuccess, __FILE__, __LINE__);
-  if (columns_on_device && scalar_fmt != BP_FR_MONT) return fail(ctx, BP_ERR_INVALID_ARG, "device columns must be Montgomery", hipSuccess, __FILE__, __LINE__);
+  if (log_n < 3 || log_n > 24) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "circuit: log_n must be in 3..24");
+  if (columns_on_device && scalar_fmt != BP_FR_MONT) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "device columns must be Montgomery");
   for (int k = 0; k < 8; k++)
     if (!columns[k]) return BP_ERR_INVALID_ARG;
   DeviceGuard guard(ctx->device);
@@ -56,7 +56,7 @@ int bp_circuit_load(bp_ctx* ctx, uint32_t log_n, const void* const columns[8], i
 int bp_circuit_free(bp_ctx* ctx, uint64_t handle) {
   if (!ctx) return BP_ERR_INVALID_ARG;
   auto it = ctx->circuits.find(handle);
-  if (it == ctx->circuits.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle", hipSuccess, __FILE__, __LINE__);
+  if (it == ctx->circuits.end()) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle");
   DeviceGuard guard(ctx->device);
   BP_HIP(ctx, stream_wait(ctx->stream));
   circuit_release(it->second);
@@ -97,7 +97,7 @@ int bp_make_s_polynomials(uint32_t log_n, const uint32_t* wire_ids, void* s1, vo
 int bp_circuit_commitments(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, uint8_t out768[768]) {
   if (!ctx || !out768) return BP_ERR_INVALID_ARG;
   auto it = ctx->circuits.find(circuit_handle);
-  if (it == ctx->circuits.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle", hipSuccess, __FILE__, __LINE__);
+  if (it == ctx->circuits.end()) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle");
   const size_t n = (size_t)1 << it->second.log_n;
   const fr_t* polys[8];
   size_t lens[8];
@@ -110,16 +110,16 @@ int bp_circuit_commitments(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_ha
 int bp_prove(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, const void* a, const void* b, const void* c, const void* public_input,
              int scalar_fmt, int witness_on_device, const uint8_t blinders[352], uint8_t proof[624]) {
   if (!ctx || !a || !b || !c || !blinders || !proof || !fmt_ok(scalar_fmt)) return BP_ERR_INVALID_ARG;
-  if (witness_on_device && scalar_fmt != BP_FR_MONT) return fail(ctx, BP_ERR_INVALID_ARG, "device witness must be Montgomery", hipSuccess, __FILE__, __LINE__);
+  if (witness_on_device && scalar_fmt != BP_FR_MONT) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "device witness must be Montgomery");
   auto it = ctx->circuits.find(circuit_handle);
-  if (it == ctx->circuits.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle", hipSuccess, __FILE__, __LINE__);
+  if (it == ctx->circuits.end()) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle");
   SrsEntry* srs;
   BP_TRY(srs_find(ctx, srs_handle, &srs));
   const size_t n = (size_t)1 << it->second.log_n;
   (void)srs;      // an SRS shorter than group_order + 6 powers truncates the commitments exactly as Setup::commit's zip does (msm.rs:29)
   fr_t blind[11];
   for (int j = 0; j < 11; j++)
-    if (!fr_from_bytes(blind[j], blinders + 32 * j, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "blinder >= q", hipSuccess, __FILE__, __LINE__);
+    if (!fr_from_bytes(blind[j], blinders + 32 * j, BP_FR_BYTES_LE)) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "blinder >= q");
   DeviceGuard guard(ctx->device);
   fr_t* wit;
   BP_TRY(ws_get(ctx, "prove.witness", 4 * n * sizeof(fr_t), (void**)&wit));

@@ -35,7 +35,7 @@ static int srs_register(bp_ctx* ctx, g1_affine* d, size_t n, size_t first, size_
 }
 int srs_find(bp_ctx* ctx, uint64_t handle, SrsEntry** out) {
   auto it = ctx->srs.find(handle);
-  if (it == ctx->srs.end()) return fail(ctx, BP_ERR_INVALID_ARG, "unknown SRS handle", hipSuccess, __FILE__, __LINE__);
+  if (it == ctx->srs.end()) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "unknown SRS handle");
   *out = &it->second;
   return BP_OK;
 }
@@ -60,7 +60,7 @@ int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, siz
 int srs_shards_checked(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, std::vector<SrsShard>* out) {
   BP_TRY(srs_shards(ctx, srs_handle, out, first, n));
   const size_t n_global = (*out)[0].e->n_global;
-  if (first > n_global || n > n_global - first) return fail(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds", hipSuccess, __FILE__, __LINE__);
+  if (first > n_global || n > n_global - first) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "SRS range out of bounds");
   return BP_OK;
 }
 
@@ -86,7 +86,7 @@ static int srs_bad_point(bp_ctx* ctx, uint64_t index, uint32_t reason, size_t* f
            reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
            : reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
                                        : "not in the prime-order subgroup");
-  return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+  return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
 }
 
 // One shard of an SRS on one device.  kind 0: decode 96-byte encodings, 1: normalise 144-byte projective images,
@@ -167,8 +167,8 @@ int bp_srs_load_compressed48(bp_ctx* ctx, const uint8_t* points48, size_t n, uin
 static int srs_generate_common(bp_ctx* ctx, size_t n, const uint8_t a32[32], const uint8_t d32[32], int mode, uint64_t* handle) {
   if (!ctx || !handle || !a32 || (mode == 1 && !d32)) return BP_ERR_INVALID_ARG;
   fr_t a, d = Fr::zero();
-  if (!fr_from_bytes(a, a32, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
-  if (mode == 1 && !fr_from_bytes(d, d32, BP_FR_BYTES_LE)) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q", hipSuccess, __FILE__, __LINE__);
+  if (!fr_from_bytes(a, a32, BP_FR_BYTES_LE)) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "scalar >= q");
+  if (mode == 1 && !fr_from_bytes(d, d32, BP_FR_BYTES_LE)) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "scalar >= q");
   return srs_make(ctx, mode == 0 ? 2 : 3, nullptr, a, d, n, handle);
 }
 int bp_srs_generate(bp_ctx* ctx, size_t powers, const uint8_t tau32[32], uint64_t* srs_handle) {
@@ -304,10 +304,9 @@ int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
   }
   const bool naf = (c & MSM_NAF_FLAG) != 0;
   if (naf && !EXPERIMENT_BUILD)        // every-position tables with NAF digits: measured slower twice, experiment builds only
-    return fail(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off) or 4..24", hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off) or 4..24");
   if (naf ? ((c & 0xffu) < 6 || (c & 0xffu) > 22 || (c >> 9)) : (c != BP_SRS_TABLES_OFF && (c < 4 || c > 24)))
-    return fail(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off), 4..24, or 256 + w (w = 6..22: every-position tables)", hipSuccess,
-                __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off), 4..24, or 256 + w (w = 6..22: every-position tables)");
   // Memory budget: the tables (rows x points x 128 B: 25.8 GB per GPU at 2^24 points) must fit beside whatever else lives on the
   // device -- a second prover context, the caller's tensors -- together with the workspaces the first MSM against them allocates.
   // The check comes BEFORE anything is released or allocated, and counts the bytes of the tables this SRS holds now as free (they
@@ -348,7 +347,7 @@ int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
     if (window_bits != 0) {
       char msg[200];
       snprintf(msg, sizeof msg, "fixed-base tables of width %u need %.1f GiB on a device with %.1f GiB free", c & 0xffu, need / 1073741824.0, free_b / 1073741824.0);
-      return fail(ctx, BP_ERR_TOO_LARGE, msg, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, BP_ERR_TOO_LARGE, msg);
     }
     uint32_t pick = BP_SRS_TABLES_OFF;
     for (uint32_t cc : {22u, 24u}) {

@@ -73,7 +73,7 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
     if (!vk_point_decode(shared_pts[k], vk768 + 96 * k)) {
       char msg[96];
       snprintf(msg, sizeof msg, "verifier key: commitment %d rejected (encoding, flags or not on the curve)", k);
-      return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
     }
   shared_pts[8] = g1_affine_generator();
   VerifyParams P;
@@ -158,13 +158,13 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
                pt_reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
                : pt_reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
                                               : "not in the prime-order subgroup");
-      return fail(ctx, BP_ERR_BAD_POINT, msg, hipSuccess, __FILE__, __LINE__);
+      return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
     }
     const uint32_t field = (uint32_t)(scalar_bad & 15);
     if (first_bad) *first_bad = sc_proof;
     snprintf(msg, sizeof msg, "proof %llu: %s is not a canonical scalar (>= q)", (unsigned long long)sc_proof,
              field < VERIFY_EVALS ? VERIFY_EVAL_NAME[field] : field == VERIFY_BAD_PUBLIC ? "a public input" : field == VERIFY_BAD_WEIGHT ? "the weight" : "a challenge");
-    return fail(ctx, BP_ERR_BAD_SCALAR, msg, hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, msg);
   }
 
   // stage 4: B over all 9 m + 9 points, A over the slice [7 m, 9 m) of the same array
@@ -194,11 +194,10 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
 int bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
                      size_t n_public, const void* weights, const void* challenges, int scalar_fmt, uint8_t out192[192], size_t* first_bad) {
   if (!ctx || !vk768 || !out192 || !fmt_ok(scalar_fmt) || (m && !proofs624) || (m && n_public && !public_inputs)) return BP_ERR_INVALID_ARG;
-  if (log_n < 3 || log_n > 28) return fail(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: log_n outside 3..28", hipSuccess, __FILE__, __LINE__);
-  if (!weights && m > 1) return fail(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: weights may be NULL for a single proof only", hipSuccess, __FILE__, __LINE__);
-  if (n_public > ((size_t)1 << log_n)) return fail(ctx, BP_ERR_LENGTH, "bp_verify_reduce: more public inputs than rows", hipSuccess, __FILE__, __LINE__);
-  if (m >= (((size_t)1 << 31) - VERIFY_SHARED + VERIFY_POINTS - 1) / VERIFY_POINTS)
-    return fail(ctx, BP_ERR_TOO_LARGE, "bp_verify_reduce: 9 m + 9 >= 2^31 points", hipSuccess, __FILE__, __LINE__);
+  if (log_n < 3 || log_n > 28) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: log_n outside 3..28");
+  if (!weights && m > 1) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce: weights may be NULL for a single proof only");
+  if (n_public > ((size_t)1 << log_n)) return BP_FAIL(ctx, BP_ERR_LENGTH, "bp_verify_reduce: more public inputs than rows");
+  if (m >= (((size_t)1 << 31) - VERIFY_SHARED + VERIFY_POINTS - 1) / VERIFY_POINTS) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "bp_verify_reduce: 9 m + 9 >= 2^31 points");
   if (first_bad) *first_bad = SIZE_MAX;
   if (m == 0) {
     encode_identity_pair(out192);

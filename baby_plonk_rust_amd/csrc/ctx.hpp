@@ -236,6 +236,7 @@ inline bool peer_path(const bp_ctx* m, int other_device) {
     hipError_t e__ = (call);                                                           \
     if (e__ != hipSuccess) return ::bp::fail(ctx, BP_ERR_HIP, #call, e__, __FILE__, __LINE__); \
   } while (0)
+#define BP_FAIL(ctx, code, text) ::bp::fail(ctx, code, text, hipSuccess, __FILE__, __LINE__)      // a refusal with no HIP error behind it
 #define BP_TRY(expr)              \
   do {                            \
     int rc__ = (expr);            \
@@ -306,6 +307,7 @@ int poly_div_run(bp_ctx* ctx, fr_t* d_a, size_t na, const fr_t* d_b, size_t nb, 
                  fr_t* d_q, size_t nq);
 int fr_nonzero_stats_run(bp_ctx* ctx, const fr_t* d_a, size_t n, size_t lo, size_t hi, size_t* eff_len, size_t* nonzero_in_range);
 int fr_compact_nonzero_run(bp_ctx* ctx, fr_t* d_q, size_t* n);
+int fr_squeeze_zeros_run(bp_ctx* ctx, fr_t* d_q, size_t* n);      // Div drops zero quotient coefficients (polynomial.rs:371-376): stats, then compact only if a zero exists
 int fr_scale_powers_run(bp_ctx* ctx, const fr_t* d_a, size_t n, const fr_t& w, fr_t* d_out);
 int fr_synthetic_run(bp_ctx* ctx, fr_t* d_out, size_t n, uint64_t seed);
 int fr_scan_mul_run(bp_ctx* ctx, const fr_t* d_in, size_t n, int reverse, int inclusive, fr_t* d_out, fr_t* d_total);

@@ -186,7 +186,7 @@ int srs_tables_run(bp_ctx* ctx, const g1_affine* d_points, const g1_affine28* d_
   const uint32_t W = msm_table_windows(c);
   const uint32_t radix = (c & MSM_NAF_FLAG) ? 0u : msm_table_radix(c, W);       // rows R^w P_i where the MSM cuts radix-R digits (MsmPlan::radix)
   if ((uint64_t)W * n >= (1ull << 31))
-    return fail(ctx, BP_ERR_TOO_LARGE, "fixed-base tables: windows * points >= 2^31", hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "fixed-base tables: windows * points >= 2^31");
   g1_affine28* t = nullptr;
   BP_HIP(ctx, hipMalloc((void**)&t, (size_t)W * (n ? n : 1) * sizeof(g1_affine28)));
   if (n) {
@@ -249,7 +249,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   *out = MsmPending();
   out->blob = d_blob != nullptr;
   if (J < 1 || J > MSM_MAX_BATCH || (J > 1 && (!table_c || d_blob)))
-    return fail(ctx, BP_ERR_INVALID_ARG, "MSM batch", hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "MSM batch");
   size_t n = 0;
   for (uint32_t j = 0; j < J; j++) n = n_each[j] > n ? n_each[j] : n;
 #ifdef BP_EXPERIMENT
@@ -266,8 +266,8 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     }
     return BP_OK;
   }
-  if (slot < 0 || slot >= MSM_SLOTS) return fail(ctx, BP_ERR_INVALID_ARG, "MSM result slot", hipSuccess, __FILE__, __LINE__);
-  if (n >= (1ull << 31)) return fail(ctx, BP_ERR_TOO_LARGE, "MSM length >= 2^31", hipSuccess, __FILE__, __LINE__);
+  if (slot < 0 || slot >= MSM_SLOTS) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "MSM result slot");
+  if (n >= (1ull << 31)) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM length >= 2^31");
   MsmPlan plan;
   make_plan(plan, n, table_c, table_stride, J);
   MsmScalars scalars_all;
@@ -276,7 +276,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     scalars_all.p[j] = j < J ? d_scalars_each[j] : nullptr;
   }
   if ((uint64_t)plan.W * n * J >= (1ull << 32))        // positions in the bucket-sorted list are 32-bit
-    return fail(ctx, BP_ERR_TOO_LARGE, "MSM length * windows >= 2^32", hipSuccess, __FILE__, __LINE__);
+    return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM length * windows >= 2^32");
   const uint32_t W = plan.W, B = plan.B, total = plan.total, Wr = table_c ? J : W;   // Wr: bucket sets left after accumulation
   const uint64_t max_entries = (uint64_t)W * n * J;
   const uint64_t n_chunks = (max_entries + plan.chunk - 1) / plan.chunk;
@@ -317,7 +317,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   BP_TRY(ws_get(ctx, "msm.bucket_sum", (size_t)total * sizeof(proj28_slot), (void**)&bucket_sum));
   BP_TRY(ws_get(ctx, "msm.partial", 2 * n_chunks * sizeof(proj28_slot), (void**)&partial));
   const uint32_t n_planes = Wr * per_window;        // tables: A and the c - 1 bit planes; else one sum per window
-  if (n_planes > (uint32_t)MSM_MAX_WINDOWS) return fail(ctx, BP_ERR_TOO_LARGE, "MSM windows", hipSuccess, __FILE__, __LINE__);
+  if (n_planes > (uint32_t)MSM_MAX_WINDOWS) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM windows");
   block_out = nullptr;
   if (reduce_running) BP_TRY(ws_get(ctx, "msm.block_out", (size_t)Wr * blocks_per_window * sizeof(proj28_slot), (void**)&block_out));
   proj28_slot* roots = nullptr;                     // table-free: the W roots (A, T_0 .. T_{c-2}) in front of the per-window Horner pass
@@ -357,7 +357,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   const uint32_t sort_env = knob_u32("BP_MSM_SORT", 2, 0, 3);      // 3: the two-level sort (first level from the scalars) at sizes where the partition sort is the default
   const bool hist_ok = plan.parts == 1 && !plan.naf && J == 1;
   const int sort_mode = (EXPERIMENT_BUILD && sort_env == 0 && hist_ok) ? 0 : ((((sort_env == 1 || sort_env == 3) && J == 1) || pb > PART_MAX_BITS) ? 1 : 2);
-  if (sort_mode != 2 && J > 1) return fail(ctx, BP_ERR_TOO_LARGE, "MSM batch too long for the partition sort", hipSuccess, __FILE__, __LINE__);
+  if (sort_mode != 2 && J > 1) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM batch too long for the partition sort");
   const uint32_t rbits = kb - pb, n_final = 1u << pb;
   // what this launch decided (bp_msm_last_path): host words only, copied into the context once everything is enqueued
   uint32_t path[12] = {J, plan.c, W, plan.radix, (uint32_t)sort_mode, pb, 0u, 0u, 0u, 0u, 0u, plan.chunk};
@@ -479,7 +479,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     else
       hipLaunchKernelGGL(msm_digit_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, fmt, plan, keys[0], vals[0], long_count + 1);
 #else
-    return fail(ctx, BP_ERR_INVALID_ARG, "records-first sort is an experiment build", hipSuccess, __FILE__, __LINE__);      // unreachable: two levels always take level 1 from the scalars
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "records-first sort is an experiment build");      // unreachable: two levels always take level 1 from the scalars
 #endif
     }
     for (int level = first_level; level < 2 && lv[level]; level++) {
@@ -524,7 +524,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     hipLaunchKernelGGL(scan_apply, dim3(n_tiles), dim3(256), 0, st, counts, total, tile_sums, offsets, cursors);
     hipLaunchKernelGGL(msm_scatter, dim3(plan.slices, W), dim3(hist_threads), hist_bytes, st, digits, plan, cursors, sorted);
 #else
-    return fail(ctx, BP_ERR_INVALID_ARG, "counting sort is an experiment build", hipSuccess, __FILE__, __LINE__);      // unreachable: sort_mode 0 needs a knob
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "counting sort is an experiment build");      // unreachable: sort_mode 0 needs a knob
 #endif
   }
   BP_HIP(ctx, hipEventRecord(ctx->ev[1], st));
@@ -736,7 +736,7 @@ int msm_finish(bp_ctx* ctx, const MsmPending& pend, g1_proj* host_out) {
   const proj28_slot* h_windows = static_cast<const proj28_slot*>(pend.h_windows);
   const uint32_t n_planes = pend.n_planes;
   const uint32_t* tail = reinterpret_cast<const uint32_t*>(h_windows + n_planes);
-  if (tail[0]) return fail(ctx, BP_ERR_BAD_SCALAR, "scalar >= q in a canonical-bytes input", hipSuccess, __FILE__, __LINE__);
+  if (tail[0]) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "scalar >= q in a canonical-bytes input");
   ctx->msm_adds = tail[1];             // entries of the bucket-sorted list = non-zero digits = bucket additions performed
   std::vector<g1_proj> windows(n_planes);
   for (uint32_t w = 0; w < n_planes; w++) windows[w] = slot_to_proj(&h_windows[w]);

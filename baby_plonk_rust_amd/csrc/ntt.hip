@@ -148,13 +148,12 @@ int ntt_tmp_buffer(bp_ctx* ctx, uint32_t k, fr_t** out) { return ws_get(ctx, "nt
 
 // phase -1: the whole transform; 0 / 1: see above (batch must be 1)
 int ntt_run_part(bp_ctx* ctx, fr_t* d_data, uint32_t k, int inverse, size_t batch, size_t stride, int phase, uint32_t part, uint32_t parts) {
-  if (k > 28) return fail(ctx, BP_ERR_TOO_LARGE, "NTT length > 2^28", hipSuccess, __FILE__, __LINE__);
+  if (k > 28) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "NTT length > 2^28");
   if (batch == 0) return BP_OK;
-  if (batch > 65535) return fail(ctx, BP_ERR_TOO_LARGE, "NTT batch > 65535", hipSuccess, __FILE__, __LINE__);
+  if (batch > 65535) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "NTT batch > 65535");
   const size_t N = (size_t)1 << k;
-  if (batch > 1 && stride < N) return fail(ctx, BP_ERR_INVALID_ARG, "NTT stride < N", hipSuccess, __FILE__, __LINE__);
-  if (phase >= 0 && (batch != 1 || !ntt_split_ok(k, parts) || part >= parts))
-    return fail(ctx, BP_ERR_INVALID_ARG, "NTT phase", hipSuccess, __FILE__, __LINE__);
+  if (batch > 1 && stride < N) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NTT stride < N");
+  if (phase >= 0 && (batch != 1 || !ntt_split_ok(k, parts) || part >= parts)) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NTT phase");
   NttPlan plan;
   make_ntt_plan(plan, k);
   NttTables* tab;

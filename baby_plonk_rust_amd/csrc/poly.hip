@@ -29,7 +29,7 @@ int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr
   uint32_t bad = 0;
   if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
-  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);
+  if (bad) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "vector element >= q");
   return BP_OK;
 }
 
@@ -37,7 +37,7 @@ int poly_eval_run(bp_ctx* ctx, const fr_t* d_coeffs, size_t n, const fr_t& x, fr
 // sequential calls were six stream waits of ~55 us each)
 int poly_eval_many_run(bp_ctx* ctx, int k, const fr_t* const* d_coeffs, const size_t* n, const fr_t* x, fr_t* host_out) {
   if (k <= 0) return BP_OK;
-  if (k > 8) return fail(ctx, BP_ERR_INVALID_ARG, "poly_eval_many: more than 8 evaluations", hipSuccess, __FILE__, __LINE__);
+  if (k > 8) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "poly_eval_many: more than 8 evaluations");
   PolyEvalMany a;
   memset(&a, 0, sizeof a);
   size_t total = 0;
@@ -140,7 +140,7 @@ int fr_nonzero_stats_run(bp_ctx* ctx, const fr_t* d_a, size_t n, size_t lo, size
 // d_q[0..*n) -> its non-zero elements in order, in place (through a workspace); *n = how many remain.  All on the device.
 int fr_compact_nonzero_run(bp_ctx* ctx, fr_t* d_q, size_t* n) {
   if (*n == 0) return BP_OK;
-  if (*n >= ((size_t)1 << 32)) return fail(ctx, BP_ERR_TOO_LARGE, "compaction longer than 2^32", hipSuccess, __FILE__, __LINE__);
+  if (*n >= ((size_t)1 << 32)) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "compaction longer than 2^32");
   const uint32_t n_tiles = (uint32_t)((*n + COMPACT_TILE - 1) / COMPACT_TILE);
   uint32_t* tiles;
   fr_t* tmp;
@@ -159,6 +159,12 @@ int fr_compact_nonzero_run(bp_ctx* ctx, fr_t* d_q, size_t* n) {
   *n = (size_t)m;
   return BP_OK;
 }
+int fr_squeeze_zeros_run(bp_ctx* ctx, fr_t* d_q, size_t* n) {
+  size_t eff, nonzero;
+  BP_TRY(fr_nonzero_stats_run(ctx, d_q, *n, 0, *n, &eff, &nonzero));      // zeros are rare, so count first
+  if (nonzero == *n) return BP_OK;
+  return fr_compact_nonzero_run(ctx, d_q, n);      // scan + scatter on the device: no proof path blocks on a host copy
+}
 int fr_scale_powers_run(bp_ctx* ctx, const fr_t* d_a, size_t n, const fr_t& w, fr_t* d_out) {
   if (n == 0) return BP_OK;
   hipLaunchKernelGGL(fr_scale_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_a, n, w, d_out);
@@ -169,7 +175,7 @@ int fr_scale_powers_run(bp_ctx* ctx, const fr_t* d_a, size_t n, const fr_t& w, f
 // out = scan of `in` by products; *d_total (device, 1 element) receives the product of all n elements
 int fr_scan_mul_run(bp_ctx* ctx, const fr_t* d_in, size_t n, int reverse, int inclusive, fr_t* d_out, fr_t* d_total) {
   const uint32_t n_tiles = (uint32_t)((n + SCANM_TILE - 1) / SCANM_TILE);
-  if (n_tiles > 256 * 64) return fail(ctx, BP_ERR_TOO_LARGE, "scan longer than 2^25", hipSuccess, __FILE__, __LINE__);
+  if (n_tiles > 256 * 64) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "scan longer than 2^25");
   fr_t* tiles;
   BP_TRY(ws_get(ctx, reverse ? "poly.scan_tiles_r" : "poly.scan_tiles_f", (size_t)(n_tiles ? n_tiles : 1) * sizeof(fr_t), (void**)&tiles));
   const size_t lds = 256 * sizeof(fr_t);
@@ -203,9 +209,9 @@ int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, 
   uint32_t bad = 0;
   if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
-  if (bad) return fail(ctx, BP_ERR_BAD_SCALAR, "vector element >= q", hipSuccess, __FILE__, __LINE__);      // before the products of such input are judged
-  if (big_is_zero(h_tot[1])) return fail(ctx, BP_ERR_DIV_ZERO, "round 2: a permutation denominator is zero (invert().unwrap())", hipSuccess, __FILE__, __LINE__);
-  if (!big_eq(h_tot[0], h_tot[1])) return fail(ctx, BP_ERR_ASSERT, "round 2: z_n != 1 (prover.rs:319)", hipSuccess, __FILE__, __LINE__);
+  if (bad) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "vector element >= q");      // before the products of such input are judged
+  if (big_is_zero(h_tot[1])) return BP_FAIL(ctx, BP_ERR_DIV_ZERO, "round 2: a permutation denominator is zero (invert().unwrap())");
+  if (!big_eq(h_tot[0], h_tot[1])) return BP_FAIL(ctx, BP_ERR_ASSERT, "round 2: z_n != 1 (prover.rs:319)");
   fr_t td_inv;
   fr_invert(td_inv, h_tot[1]);
   hipLaunchKernelGGL(grand_product_combine, dim3(blocks), dim3(256), 0, ctx->stream, pn, sd, td_inv, n, d_z);

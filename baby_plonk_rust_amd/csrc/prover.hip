@@ -79,14 +79,6 @@ int commit(bp_ctx* ctx, uint64_t srs, const fr_t* d_coeffs, size_t n, g1_proj* o
   return BP_OK;
 }
 
-// the reference's Div drops zero quotient coefficients (polynomial.rs:371-376): compact d_q[0..n) in place
-int squeeze_zeros(bp_ctx* ctx, fr_t* d_q, size_t* n) {
-  size_t eff, nonzero;
-  BP_TRY(fr_nonzero_stats_run(ctx, d_q, *n, 0, *n, &eff, &nonzero));
-  if (nonzero == *n) return BP_OK;
-  return fr_compact_nonzero_run(ctx, d_q, n);      // scan + scatter on the device: no proof path blocks on a host copy
-}
-
 // (numerator of na coefficients) / (x - point) -> d_q, *nq coefficients, by the reference's Div semantics
 int divide_by_linear(bp_ctx* ctx, fr_t* d_num, size_t na, const fr_t& point, fr_t* d_q, size_t* nq) {
   size_t na_eff, dummy;
@@ -99,7 +91,7 @@ int divide_by_linear(bp_ctx* ctx, fr_t* d_num, size_t na, const fr_t& point, fr_
   BP_HIP(ctx, hipMemcpyAsync(d_b, hb, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
   *nq = na_eff - 1;
   BP_TRY(poly_div_run(ctx, d_num, na_eff, d_b, 2, hb[0], hb[1], true, d_q, *nq));
-  return squeeze_zeros(ctx, d_q, nq);
+  return fr_squeeze_zeros_run(ctx, d_q, nq);
 }
 
 constexpr uint64_t COSET_GEN = 7;        // generator of Fr^* (scalar.rs GENERATOR): g^n w^j != 1 for every n-th-root coset used here
@@ -533,9 +525,9 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
   BP_TRY(fr_nonzero_stats_run(ctx, t, N, 0, 0, &t_len, &dummy));
   // deg(numerator) <= 4n + 5, so an exact quotient has at most 3n + 6 coefficients; anything longer means the division by
   // x^n - 1 left a remainder, i.e. the witness does not satisfy the circuit (the reference would panic at prover.rs:615)
-  if (t_len > 3 * n + 6) return fail(ctx, BP_ERR_ASSERT, "round 3: constraints not divisible by x^n - 1 (witness does not satisfy the circuit)", hipSuccess, __FILE__, __LINE__);
-  BP_TRY(squeeze_zeros(ctx, t, &t_len));
-  if (t_len <= 2 * n) return fail(ctx, BP_ERR_ASSERT, "round 3: quotient shorter than 2n + 1 (t_hi would be empty; values[0] panics)", hipSuccess, __FILE__, __LINE__);
+  if (t_len > 3 * n + 6) return BP_FAIL(ctx, BP_ERR_ASSERT, "round 3: constraints not divisible by x^n - 1 (witness does not satisfy the circuit)");
+  BP_TRY(fr_squeeze_zeros_run(ctx, t, &t_len));
+  if (t_len <= 2 * n) return BP_FAIL(ctx, BP_ERR_ASSERT, "round 3: quotient shorter than 2n + 1 (t_hi would be empty; values[0] panics)");
   // split_t_to_3pieces (:649-659) and the blinding of :475-481
   fr_t *t_lo, *t_mid, *t_hi;
   BP_TRY(ws_get(ctx, "prove.t_parts", 3 * (n + 8) * sizeof(fr_t), (void**)&t_lo));
@@ -619,14 +611,14 @@ int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_
   BP_TRY(ws_get(ctx, "prove.num", (n + 16) * sizeof(fr_t), (void**)&num));
   BP_TRY(ws_get(ctx, "prove.w", 2 * (n + 16) * sizeof(fr_t), (void**)&w_zeta));
   w_zeta_omega = w_zeta + (n + 16);
-  if (num_len > n + 16) return fail(ctx, BP_ERR_ASSERT, "round 5: quotient piece longer than n + 16", hipSuccess, __FILE__, __LINE__);
+  if (num_len > n + 16) return BP_FAIL(ctx, BP_ERR_ASSERT, "round 5: quotient piece longer than n + 16");
   hipLaunchKernelGGL(fr_lincomb, dim3((unsigned)((num_len + 255) / 256)), dim3(256), 0, st, lc, num, num_len);
   BP_HIP(ctx, hipGetLastError());
   // r(zeta) == 0 (prover.rs:615): the opening terms vanish at zeta, so the numerator's value there is r's
   fr_t check;
   BP_TRY(poly_eval_run(ctx, num, num_len, zeta, &check));
   (void)r_terms;
-  if (!big_is_zero(check)) return fail(ctx, BP_ERR_ASSERT, "round 5: r(zeta) != 0 (prover.rs:615)", hipSuccess, __FILE__, __LINE__);
+  if (!big_is_zero(check)) return BP_FAIL(ctx, BP_ERR_ASSERT, "round 5: r(zeta) != 0 (prover.rs:615)");
   size_t wz_len, wzo_len;
   BP_TRY(divide_by_linear(ctx, num, num_len, zeta, w_zeta, &wz_len));
   // W_zeta_omega = (z - z_omega_bar) / (x - zeta w)  (:636-638)

@@ -16,7 +16,7 @@ int srs_decode_run(bp_ctx* ctx, const uint8_t* d_bytes, size_t n, g1_affine* d_o
   uint32_t h = 0;
   BP_HIP(ctx, hipMemcpyAsync(&h, status, 4, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
-  if (h) return fail(ctx, BP_ERR_BAD_POINT, h & 1 ? "non-canonical point encoding" : "point not on the curve", hipSuccess, __FILE__, __LINE__);
+  if (h) return BP_FAIL(ctx, BP_ERR_BAD_POINT, h & 1 ? "non-canonical point encoding" : "point not on the curve");
   return BP_OK;
 }
 int srs_encode_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes) {

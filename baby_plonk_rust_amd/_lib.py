@@ -86,7 +86,9 @@ SIGNATURES = {
     "bp_transcript_test_vector": (_int, [_vp]),
     "bp_plonk_challenges": (_int, [_vp, _sz, _int, _vp, _pp(_sz)]),
     "bp_verify_reduce": (_int, [_vp, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _int, _vp, _pp(_sz)]),
+    "bp_verify_reduce_segments": (_int, [_vp, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _int, _sz, _vp, _pp(_sz)]),
     "bp_verify_last_stats": (_int, [_vp, _vp]),
+    "bp_verify_segments_last_stats": (_int, [_vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

@@ -358,6 +358,28 @@ class Context:
         """fill HBM at `ptr` with n synthetic Montgomery scalars (the same stream the CPU baseline uses)"""
         self.check(self._lib.bp_fr_synthetic_device(self._h, ptr, n, seed), "bp_fr_synthetic_device")
 
+    def _verify_args(self, what, vk, proofs, public_inputs, weights, challenges, fmt):
+        """the arguments bp_verify_reduce and bp_verify_reduce_segments share, as arrays: (vk, records, m, publics, n_public, weights, challenges)"""
+        if isinstance(vk, dict):
+            vk = b"".join(vk[k] for k in CIRCUIT_COLUMNS)
+        vkb = np.frombuffer(bytes(vk), dtype=np.uint8).copy()
+        if len(vkb) != 768:
+            raise BpError(-1, what, "vk: eight 96-byte commitments expected")
+        rec, m = _proof_records(proofs)
+
+        def scalars(a, per_proof, name):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(a, dtype=np.uint64 if fmt == FR_MONT else np.uint8)
+            width = 4 if fmt == FR_MONT else 32
+            if a.size % width or (a.size // width) % max(m, 1) or (per_proof is not None and a.size != m * per_proof * width):
+                raise BpError(-6, what, "%s: %d scalars do not fit %d proofs" % (name, a.size // width, m))
+            return a, (a.size // width // m if m else 0)
+        pub, n_public = scalars(public_inputs, None, "public_inputs")
+        w, _ = scalars(weights, 1, "weights")
+        ch, _ = scalars(challenges, 6, "challenges")
+        return vkb, rec, m, pub, n_public, w, ch
+
     def verify_reduce(self, log_n, vk, proofs, public_inputs=None, weights=None, challenges=None, fmt=FR_MONT):
         """Verifier::verify (verifier.rs:80-192) of m proofs of one circuit up to the two pairings (bp_verify_reduce): returns
         (A96, B96); the batch is valid iff pairing(A, x_2) == pairing(B, G2 generator).  vk: the 768 bytes of
@@ -366,24 +388,7 @@ class Context:
         (None: a single proof, weight 1); challenges: None = the reference's transcript on the device, else [m, 6] scalars
         beta gamma alpha zeta nu mu.  Scalars: [.., 4] uint64 Montgomery limbs (fmt=FR_MONT) or [.., 32] uint8 canonical
         little-endian bytes (fmt=FR_BYTES_LE).  A rejected proof raises BpError whose `index` is the lowest failing proof."""
-        if isinstance(vk, dict):
-            vk = b"".join(vk[k] for k in CIRCUIT_COLUMNS)
-        vkb = np.frombuffer(bytes(vk), dtype=np.uint8).copy()
-        if len(vkb) != 768:
-            raise BpError(-1, "verify_reduce", "vk: eight 96-byte commitments expected")
-        rec, m = _proof_records(proofs)
-
-        def scalars(a, per_proof, what):
-            if a is None:
-                return None, 0
-            a = np.ascontiguousarray(a, dtype=np.uint64 if fmt == FR_MONT else np.uint8)
-            width = 4 if fmt == FR_MONT else 32
-            if a.size % width or (a.size // width) % max(m, 1) or (per_proof is not None and a.size != m * per_proof * width):
-                raise BpError(-6, "verify_reduce", "%s: %d scalars do not fit %d proofs" % (what, a.size // width, m))
-            return a, (a.size // width // m if m else 0)
-        pub, n_public = scalars(public_inputs, None, "public_inputs")
-        w, _ = scalars(weights, 1, "weights")
-        ch, _ = scalars(challenges, 6, "challenges")
+        vkb, rec, m, pub, n_public, w, ch = self._verify_args("verify_reduce", vk, proofs, public_inputs, weights, challenges, fmt)
         out, bad = np.zeros(192, dtype=np.uint8), C.c_size_t()
         rc = self._lib.bp_verify_reduce(self._h, log_n, vkb.ctypes.data, rec.ctypes.data if m else None, m,
                                         pub.ctypes.data if pub is not None and pub.size else None, n_public,
@@ -396,11 +401,37 @@ class Context:
             raise
         return out[:96].tobytes(), out[96:].tobytes()
 
+    def verify_reduce_segments(self, log_n, vk, proofs, public_inputs=None, weights=None, challenges=None, fmt=FR_MONT, segment=1):
+        """verify_reduce per segment of the batch (bp_verify_reduce_segments): a list of ceil(m / segment) pairs (A96, B96), pair s
+        being what verify_reduce returns for the proofs [s * segment, (s + 1) * segment) alone.  segment=1: one pair per proof
+        (weights may then be None: weight 1 each).  Arguments and errors as verify_reduce."""
+        vkb, rec, m, pub, n_public, w, ch = self._verify_args("verify_reduce_segments", vk, proofs, public_inputs, weights, challenges, fmt)
+        segment = int(segment)
+        n_seg = -(-m // segment) if segment > 0 else 0
+        out, bad = np.zeros(max(n_seg, 1) * 192, dtype=np.uint8), C.c_size_t()
+        rc = self._lib.bp_verify_reduce_segments(self._h, log_n, vkb.ctypes.data, rec.ctypes.data if m else None, m,
+                                                 pub.ctypes.data if pub is not None and pub.size else None, n_public,
+                                                 None if w is None else w.ctypes.data, None if ch is None else ch.ctypes.data, fmt,
+                                                 max(segment, 0), out.ctypes.data, C.byref(bad))
+        try:
+            self.check(rc, "bp_verify_reduce_segments")
+        except BpError as e:
+            e.index = bad.value if rc in (-3, -4) and bad.value != C.c_size_t(-1).value else None
+            raise
+        raw = out.tobytes()
+        return [(raw[192 * s: 192 * s + 96], raw[192 * s + 96: 192 * s + 192]) for s in range(n_seg)]
+
     def verify_stats(self):
         """HIP-event milliseconds of the five stages of the last verify_reduce"""
         ms = (C.c_float * 5)()
         self.check(self._lib.bp_verify_last_stats(self._h, ms), "bp_verify_last_stats")
         return dict(zip(("upload_ms", "transcript_ms", "scalars_ms", "decode_check_ms", "msm_ms"), [float(v) for v in ms]))
+
+    def verify_segments_stats(self):
+        """HIP-event milliseconds of the last stage of the last verify_reduce_segments, in its three parts"""
+        ms = (C.c_float * 3)()
+        self.check(self._lib.bp_verify_segments_last_stats(self._h, ms), "bp_verify_segments_last_stats")
+        return dict(zip(("mul_ms", "reduce_ms", "encode_ms"), [float(v) for v in ms]))
 
     def set_stream(self, stream_ptr):
         self.check(self._lib.bp_set_stream(self._h, stream_ptr), "bp_set_stream")
@@ -908,3 +939,41 @@ class Verifier:
         """proofs: m x 624 bytes; public_inputs: [m, n_public] scalars (None: no public inputs); weights: m scalars the caller drew
         after it received the proofs, >= 128 bits of entropy each (None for a single proof)."""
         return self.ctx.verify_reduce(self.group_order.bit_length() - 1, self.vk, proofs, public_inputs, weights, challenges, fmt)
+
+    def pairing_inputs_segments(self, proofs, public_inputs, weights=None, challenges=None, fmt=FR_MONT, segment=1):
+        """one pair (A_s, B_s) per segment of `segment` consecutive proofs: pair s is pairing_inputs of that slice alone
+        (weights may be None only with segment=1)"""
+        return self.ctx.verify_reduce_segments(self.group_order.bit_length() - 1, self.vk, proofs, public_inputs, weights, challenges, fmt, segment)
+
+    def locate_invalid(self, proofs, public_inputs, weights, decide, fmt=FR_MONT):
+        """the sorted indices of the proofs of a batch whose own pair fails decide(A96, B96) -> bool, the host's pairing check
+        (pairing(A, x_2) == pairing(B, G2 generator)); the library computes no pairing.  ONE GPU call with segment=1 gives a pair
+        per proof; a range's pair is the host sum of its leaves (bp_g1_sum_partials over 144-byte partials), and the search
+        descends only into ranges whose sum fails: at most 1 + 2 k ceil(log2 m) decide calls for k bad proofs, 1 for a good batch.
+        weights: as pairing_inputs -- they make the sums sound (a failing range may not hide behind cancelling terms)."""
+        leaves = self.pairing_inputs_segments(proofs, public_inputs, weights, None, fmt, 1)
+        m = len(leaves)
+        part_a = b"".join(bytes96_to_partial(a) for a, _ in leaves)
+        part_b = b"".join(bytes96_to_partial(b) for _, b in leaves)
+
+        def fails(lo, hi):
+            if hi - lo == 1:
+                return not decide(*leaves[lo])
+            return not decide(sum_partials(part_a[144 * lo: 144 * hi]), sum_partials(part_b[144 * lo: 144 * hi]))
+        bad = []
+        todo = [(0, m, None)] if m else []                      # (lo, hi, known to fail?)
+        while todo:
+            lo, hi, known = todo.pop()
+            if not (known or fails(lo, hi)):
+                continue
+            if hi - lo == 1:
+                bad.append(lo)
+                continue
+            mid = (lo + hi + 1) // 2
+            # a failing range whose left half passes has its failure on the right: that half needs no decide call of its own
+            if fails(lo, mid):
+                todo.append((lo, mid, True))
+                todo.append((mid, hi, None))
+            else:
+                todo.append((mid, hi, True))
+        return sorted(bad)

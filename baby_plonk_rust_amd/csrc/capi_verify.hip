@@ -10,6 +10,7 @@
 #include "ctx.hpp"
 #include "g1_check.hpp"
 #include "verify_kernels.hpp"
+#include "verify_segments_kernels.hpp"
 
 #include "capi_common.hpp"
 
@@ -65,10 +66,21 @@ static int verify_events(bp_ctx* ctx) {
   return BP_OK;
 }
 
-static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
-                             size_t n_public, const void* weights, const void* challenges, int fmt, uint8_t out192[192], size_t* first_bad) {
+// what stages 0-3 leave on the device for stage 4, whichever it is
+struct VerifyStaged {
+  size_t m = 0, n_pts = 0, n_all = 0;      // proofs, 9 m proof points, 9 m + 9 points with the shared bases behind them
+  fr_t *d_b = nullptr, *d_a = nullptr;     // verify_scalars' scal_b (9 m, and nine free slots behind) and scal_a (2 m)
+  fr_t* d_sh = nullptr;                    // its per-proof shares of the nine shared-base scalars (9 m)
+  g1_affine* d_pts = nullptr;              // the decoded points, column-major, then the nine shared bases
+  g1_affine shared_pts[VERIFY_SHARED];     // the shared bases as uploaded: eight vk commitments and G
+};
+
+// Stages 0-3 of both entry points: upload, transcript, scalars (with the batch-wide shared sums behind scal_b), decode + subgroup
+// check, and the rejection path that names the lowest proof.  Records ev[0..4]; returns with the stream idle.
+static int verify_stages_0_3(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                             size_t n_public, const void* weights, const void* challenges, int fmt, size_t* first_bad, VerifyStaged* staged) {
   // the nine shared bases: eight vk commitments in the order bp_circuit_commitments writes them, then G
-  g1_affine shared_pts[VERIFY_SHARED];
+  g1_affine* shared_pts = staged->shared_pts;
   for (int k = 0; k < 8; k++)
     if (!vk_point_decode(shared_pts[k], vk768 + 96 * k)) {
       char msg[96];
@@ -88,7 +100,6 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   uint8_t *d_rec, *d_comp;
   fr_t *d_chal, *d_w = nullptr, *d_pub = nullptr, *d_b, *d_a, *d_sh;
   g1_affine* d_pts;
-  g1_affine28* d_p28;
   unsigned long long* d_status;
   BP_TRY(ws_get(ctx, "verify.records", m * VERIFY_RECORD_BYTES, (void**)&d_rec));
   BP_TRY(ws_get(ctx, "verify.comp", n_pts * 48, (void**)&d_comp));
@@ -99,7 +110,6 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   BP_TRY(ws_get(ctx, "verify.scal_a", 2 * m * sizeof(fr_t), (void**)&d_a));
   BP_TRY(ws_get(ctx, "verify.shared", n_pts * sizeof(fr_t), (void**)&d_sh));
   BP_TRY(ws_get(ctx, "verify.points", n_all * sizeof(g1_affine), (void**)&d_pts));
-  BP_TRY(ws_get(ctx, "verify.p28", n_all * sizeof(g1_affine28), (void**)&d_p28));
   BP_TRY(ws_get(ctx, "verify.status", 8, (void**)&d_status));
   BP_TRY(verify_events(ctx));
   hipStream_t st = ctx->stream;
@@ -111,7 +121,7 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   if (challenges) BP_HIP(ctx, hipMemcpyAsync(d_chal, challenges, m * 6 * sizeof(fr_t), hipMemcpyHostToDevice, st));
   if (weights) BP_HIP(ctx, hipMemcpyAsync(d_w, weights, m * sizeof(fr_t), hipMemcpyHostToDevice, st));
   if (n_public) BP_HIP(ctx, hipMemcpyAsync(d_pub, public_inputs, m * n_public * sizeof(fr_t), hipMemcpyHostToDevice, st));
-  BP_HIP(ctx, hipMemcpyAsync(d_pts + n_pts, shared_pts, sizeof shared_pts, hipMemcpyHostToDevice, st));
+  BP_HIP(ctx, hipMemcpyAsync(d_pts + n_pts, shared_pts, sizeof staged->shared_pts, hipMemcpyHostToDevice, st));
   BP_HIP(ctx, hipMemsetAsync(d_status, 0xff, 8, st));
   // stage 1: transcript
   BP_HIP(ctx, hipEventRecord(ev[1], st));
@@ -167,6 +177,28 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
     return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, msg);
   }
 
+  staged->m = m;
+  staged->n_pts = n_pts;
+  staged->n_all = n_all;
+  staged->d_b = d_b;
+  staged->d_a = d_a;
+  staged->d_sh = d_sh;
+  staged->d_pts = d_pts;
+  return BP_OK;
+}
+
+static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                             size_t n_public, const void* weights, const void* challenges, int fmt, uint8_t out192[192], size_t* first_bad) {
+  VerifyStaged V;
+  BP_TRY(verify_stages_0_3(ctx, log_n, vk768, proofs624, m, public_inputs, n_public, weights, challenges, fmt, first_bad, &V));
+  const size_t n_all = V.n_all;
+  fr_t *d_b = V.d_b, *d_a = V.d_a;
+  g1_affine* d_pts = V.d_pts;
+  g1_affine28* d_p28;
+  BP_TRY(ws_get(ctx, "verify.p28", n_all * sizeof(g1_affine28), (void**)&d_p28));
+  hipStream_t st = ctx->stream;
+  hipEvent_t* ev = ctx->verify_ev;
+
   // stage 4: B over all 9 m + 9 points, A over the slice [7 m, 9 m) of the same array
   BP_TRY(srs_to28_into(ctx, d_pts, n_all, d_p28));
   MsmPending pend_b, pend_a;
@@ -191,6 +223,81 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   return BP_OK;
 }
 
+// the eight commitments of the verifier key all in the prime-order subgroup?  (The key is checked for the curve only: the reference
+// verifier does no more.)  ~9 000 field products on the host, so the answer is kept with the key's bytes: a service verifies batch
+// after batch against one key.
+static bool vk_in_subgroup(bp_ctx* ctx, const uint8_t vk768[768], const g1_affine shared_pts[VERIFY_SHARED]) {
+  if (ctx->verify_vk_seen.size() == 769 && memcmp(ctx->verify_vk_seen.data(), vk768, 768) == 0) return ctx->verify_vk_seen[768] != 0;
+  bool ok = true;
+  for (int k = 0; k < 8 && ok; k++) ok = g1_is_torsion_free(shared_pts[k]);
+  ctx->verify_vk_seen.assign(vk768, vk768 + 768);
+  ctx->verify_vk_seen.push_back(ok ? 1 : 0);
+  return ok;
+}
+
+// Stage 4 of bp_verify_reduce_segments: T = 11 m + 9 S products, one per lane, then the sums (verify_segments_kernels.hpp).
+static int verify_segments_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                               size_t n_public, const void* weights, const void* challenges, int fmt, size_t segment, uint8_t* out192,
+                               size_t* first_bad) {
+  VerifyStaged V;
+  BP_TRY(verify_stages_0_3(ctx, log_n, vk768, proofs624, m, public_inputs, n_public, weights, challenges, fmt, first_bad, &V));
+  const size_t seg = std::min(segment, m), S = (m + seg - 1) / seg;
+  const size_t n_terms = (size_t)(VERIFY_POINTS + 2) * m, T = n_terms + (size_t)VERIFY_SHARED * S;
+  fr_t* d_seg;
+  uint32_t *d_prod, *d_node, *d_run;
+  uint8_t* d_out;
+  BP_TRY(ws_get(ctx, "verify.seg_scal", (size_t)VERIFY_SHARED * S * sizeof(fr_t), (void**)&d_seg));
+  BP_TRY(ws_get(ctx, "verify.seg_prod", T * SEG_PT_WORDS * sizeof(uint32_t), (void**)&d_prod));
+  BP_TRY(ws_get(ctx, "verify.seg_node", 2 * m * SEG_PT_WORDS * sizeof(uint32_t), (void**)&d_node));
+  BP_TRY(ws_get(ctx, "verify.seg_run", 2 * S * N28 * sizeof(uint32_t), (void**)&d_run));
+  BP_TRY(ws_get(ctx, "verify.seg_out", S * 192, (void**)&d_out));
+  for (auto& e : ctx->verify_seg_ev)
+    if (!e) BP_HIP(ctx, hipEventCreate(&e));
+  hipStream_t st = ctx->stream;
+  hipEvent_t *ev = ctx->verify_ev, *sev = ctx->verify_seg_ev;
+  auto blocks = [](size_t n, size_t per) { return dim3((unsigned)((n + per - 1) / per)); };
+
+  // the shared-base terms take the split form only where the endomorphism is [x^2]: on a key inside the subgroup
+  size_t plain_from = vk_in_subgroup(ctx, vk768, V.shared_pts) ? T : n_terms;
+  if (const char* v = knob("BP_VERIFY_SEG_PLAIN"))                  // experiment build: the A/B of docs/EXPERIMENTS.md
+    if (*v && *v != '0') plain_from = 0;
+  uint32_t L = 1;                                                   // lanes per segmented scalar sum
+  while (L < 256 && L < seg) L <<= 1;
+  hipLaunchKernelGGL(verify_seg_shared_sum, blocks((size_t)VERIFY_SHARED * S, 256 / L), dim3(256), 0, st, V.d_sh, m, seg, S, L, d_seg);
+  BP_HIP(ctx, hipGetLastError());
+  if (plain_from > 0) {
+    hipLaunchKernelGGL(verify_seg_mul<true>, blocks(plain_from, 64), dim3(64), 0, st, V.d_pts, V.d_b, V.d_a, d_seg, m, S, (size_t)0, plain_from, d_prod);
+    BP_HIP(ctx, hipGetLastError());
+  }
+  if (plain_from < T) {
+    hipLaunchKernelGGL(verify_seg_mul<false>, blocks(T - plain_from, 64), dim3(64), 0, st, V.d_pts, V.d_b, V.d_a, d_seg, m, S, plain_from, T, d_prod);
+    BP_HIP(ctx, hipGetLastError());
+  }
+  BP_HIP(ctx, hipEventRecord(sev[0], st));
+  hipLaunchKernelGGL(verify_seg_proof_sum, blocks(2 * m, 64), dim3(64), 0, st, d_prod, T, m, d_node);
+  BP_HIP(ctx, hipGetLastError());
+  for (size_t d = 1; d < seg; d <<= 1) {
+    const size_t slots = (seg + 2 * d - 1) / (2 * d);
+    hipLaunchKernelGGL(verify_seg_tree, blocks(2 * S * slots, 64), dim3(64), 0, st, d_node, m, seg, S, d, slots);
+    BP_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(verify_seg_add_shared, blocks(S, 64), dim3(64), 0, st, d_node, m, seg, S, d_prod, T);
+  BP_HIP(ctx, hipGetLastError());
+  BP_HIP(ctx, hipEventRecord(sev[1], st));
+  // one inversion per pair at the least, per eight points where there are lanes to spare
+  const uint32_t group = 2 * S >= ((size_t)1 << 15) ? 8 : 2 * S >= ((size_t)1 << 12) ? 4 : 2;
+  hipLaunchKernelGGL(verify_seg_encode, blocks((2 * S + group - 1) / group, 64), dim3(64), 0, st, d_node, m, seg, S, group, d_run, d_out);
+  BP_HIP(ctx, hipGetLastError());
+  BP_HIP(ctx, hipEventRecord(ev[5], st));
+  BP_HIP(ctx, hipMemcpyAsync(out192, d_out, S * 192, hipMemcpyDeviceToHost, st));
+  BP_HIP(ctx, stream_wait(st));
+  for (int k = 0; k < 5; k++) BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_ms[k], ev[k], ev[k + 1]));
+  BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_seg_ms[0], ev[4], sev[0]));
+  BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_seg_ms[1], sev[0], sev[1]));
+  BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_seg_ms[2], sev[1], ev[5]));
+  return BP_OK;
+}
+
 int bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
                      size_t n_public, const void* weights, const void* challenges, int scalar_fmt, uint8_t out192[192], size_t* first_bad) {
   if (!ctx || !vk768 || !out192 || !fmt_ok(scalar_fmt) || (m && !proofs624) || (m && n_public && !public_inputs)) return BP_ERR_INVALID_ARG;
@@ -209,8 +316,33 @@ int bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], cons
   return verify_reduce_run(ctx, log_n, vk768, proofs624, m, public_inputs, n_public, weights, challenges, scalar_fmt, out192, first_bad);
 }
 
+int bp_verify_reduce_segments(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m, const void* public_inputs,
+                              size_t n_public, const void* weights, const void* challenges, int scalar_fmt, size_t segment, uint8_t* out192,
+                              size_t* first_bad) {
+  if (!ctx || !vk768 || !fmt_ok(scalar_fmt) || (m && (!proofs624 || !out192)) || (m && n_public && !public_inputs)) return BP_ERR_INVALID_ARG;
+  if (log_n < 3 || log_n > 28) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce_segments: log_n outside 3..28");
+  if (segment == 0) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce_segments: segment is 0");
+  if (!weights && m > 1 && segment != 1)
+    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "bp_verify_reduce_segments: weights may be NULL only where every segment is a single proof");
+  if (n_public > ((size_t)1 << log_n)) return BP_FAIL(ctx, BP_ERR_LENGTH, "bp_verify_reduce_segments: more public inputs than rows");
+  if (m >= (((size_t)1 << 31) - VERIFY_SHARED + VERIFY_POINTS - 1) / VERIFY_POINTS)
+    return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "bp_verify_reduce_segments: 9 m + 9 >= 2^31 points");
+  if (first_bad) *first_bad = SIZE_MAX;
+  for (float& v : ctx->verify_ms) v = 0;
+  for (float& v : ctx->verify_seg_ms) v = 0;
+  if (m == 0) return BP_OK;
+  DeviceGuard guard(ctx->device);
+  return verify_segments_run(ctx, log_n, vk768, proofs624, m, public_inputs, n_public, weights, challenges, scalar_fmt, segment, out192, first_bad);
+}
+
 int bp_verify_last_stats(bp_ctx* ctx, float stage_ms[5]) {
   if (!ctx || !stage_ms) return BP_ERR_INVALID_ARG;
   for (int k = 0; k < 5; k++) stage_ms[k] = ctx->verify_ms[k];
+  return BP_OK;
+}
+
+int bp_verify_segments_last_stats(bp_ctx* ctx, float split_ms[3]) {
+  if (!ctx || !split_ms) return BP_ERR_INVALID_ARG;
+  for (int k = 0; k < 3; k++) split_ms[k] = ctx->verify_seg_ms[k];
   return BP_OK;
 }

@@ -128,6 +128,11 @@ struct bp_ctx {
   hipEvent_t side_ev[2] = {nullptr, nullptr};
   hipEvent_t verify_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // bp_verify_reduce: the boundaries of its five stages
   float verify_ms[5] = {0, 0, 0, 0, 0};              // upload, transcript, scalars, decode + subgroup check, MSMs of the last bp_verify_reduce
+  // bp_verify_reduce_segments: the two boundaries inside its last stage, and that stage's split (multiplications | per-proof sums,
+  // segment tree and shared bases | normalisation and encoding)
+  hipEvent_t verify_seg_ev[2] = {nullptr, nullptr};
+  float verify_seg_ms[3] = {0, 0, 0};
+  std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
   hipEvent_t seam_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // bp_msm_g1_projective144: piece k uploaded and normalised (recorded on the side stream)
   hipStream_t stream = nullptr;
   bool own_stream = true;

@@ -452,9 +452,26 @@ int  bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, voi
 int  bp_verify_reduce(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m,
                       const void* public_inputs, size_t n_public, const void* weights, const void* challenges,
                       int scalar_fmt, uint8_t out192[192], size_t* first_bad);
-/* HIP-event milliseconds of the stages of the last bp_verify_reduce: upload, transcript, scalars, decode + subgroup check, MSMs
- * (all 0 after an empty or a rejected batch). */
+/* The same reduction per SEGMENT of the batch: segment s covers the proofs [s * segment, min(m, (s + 1) * segment)), there are
+ * S = ceil(m / segment) of them (the last may be short), and out192 receives S x 192 bytes, A_s || B_s.  A_s || B_s is byte for
+ * byte what bp_verify_reduce returns for that slice of the proofs, public-input rows, weights and challenges alone: segment == 1
+ * gives one pair per proof, segment >= m the one pair of bp_verify_reduce.  With segment == 1 a failing batch is located in ONE
+ * call: the host sums the leaves of a range (bp_g1_bytes96_to_partial, bp_g1_sum_partials) and bisects with its pairing check.
+ * weights == NULL (rho_j = 1) is accepted only when segment == 1 or m <= 1 -- a sum over several proofs needs caller-drawn
+ * weights -- else BP_ERR_INVALID_ARG, as is segment == 0.  Every other argument rule, check and error is bp_verify_reduce's; any
+ * rejection rejects the whole call and leaves out192 untouched.  m == 0: BP_OK, nothing written.  The work is 11 m + 9 S
+ * variable-base multiplications, one per GPU lane, then short sums (no bucket MSM: a 20-term sum has no use for one).  Blocking;
+ * ordered on the context's stream; a bp_init_multi context runs on its primary device. */
+int  bp_verify_reduce_segments(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[768], const uint8_t* proofs624, size_t m,
+                               const void* public_inputs, size_t n_public, const void* weights, const void* challenges,
+                               int scalar_fmt, size_t segment, uint8_t* out192, size_t* first_bad);
+/* HIP-event milliseconds of the stages of the last bp_verify_reduce or bp_verify_reduce_segments: upload, transcript, scalars,
+ * decode + subgroup check, and the MSMs -- after bp_verify_reduce_segments: its multiplications, sums and encoding -- (all 0 after an
+ * empty or a rejected batch). */
 int  bp_verify_last_stats(bp_ctx* ctx, float stage_ms[5]);
+/* The last stage of the last bp_verify_reduce_segments split in three: the multiplications; the per-proof sums, the segment tree and
+ * the shared bases; normalisation and encoding. */
+int  bp_verify_segments_last_stats(bp_ctx* ctx, float split_ms[3]);
 
 #ifdef __cplusplus
 }

@@ -1,16 +1,11 @@
 // capi_prove.hip -- C ABI, part 5: the native prover (circuit preprocessing, bp_prove, transcript test vector).
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "ctx.hpp"
+#include "transcript.hpp"
 
 #include "capi_common.hpp"
 
@@ -42,12 +37,10 @@ int bp_circuit_load(bp_ctx* ctx, uint32_t log_n, const void* const columns[8], i
     (void)hipFree(lag);
     return rc;
   }
-  if (is_group(ctx) || knob_u32("BP_PROVE_COSET_ONE", 0, 0, 1) == 1) {       // round 3 by coset over the members: their shares of the coset tables (experiment: one device, all four)
-    rc = circuit_split_build(ctx, e);
-    if (rc != BP_OK) {
-      circuit_release(e);
-      return rc;
-    }
+  rc = circuit_split_build(ctx, e);      // round 3 by coset over the members of a group: their shares of the coset tables (nothing otherwise)
+  if (rc != BP_OK) {
+    circuit_release(e);
+    return rc;
   }
   *handle = ctx->next_handle++;
   ctx->circuits[*handle] = e;
@@ -71,12 +64,7 @@ int bp_make_s_polynomials(uint32_t log_n, const uint32_t* wire_ids, void* s1, vo
   std::vector<fr_t> root(n);                                  // roots_of_unity(group_order), utils.rs:45-52
   root[0] = Fr::one();
   for (size_t i = 1; i < n; i++) Fr::mul(root[i], root[i - 1], w);
-  fr_t col[3], two, three;
-  col[0] = Fr::one();
-  Fr::add(two, col[0], col[0]);
-  Fr::add(three, two, col[0]);
-  col[1] = two;
-  col[2] = three;
+  const fr_t col[3] = {Fr::one(), fr_from_u64(2), fr_from_u64(3)};
   auto label = [&](size_t cell) { fr_t r; Fr::mul(r, root[cell / 3], col[cell % 3]); return r; };      // Cell::label, utils.rs:28-37
   // cells grouped by variable, row-major inside a group (program.rs:80-99)
   std::vector<uint64_t> order(cells);
@@ -124,14 +112,8 @@ int bp_prove(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, const vo
   fr_t* wit;
   BP_TRY(ws_get(ctx, "prove.witness", 4 * n * sizeof(fr_t), (void**)&wit));
   const void* cols[4] = {a, b, c, public_input};
-  // host witness of 2^18 gates and more on one device: round 1 stages the columns itself, uploads beside the commitments (BP_PROVE_STAGED=0: off)
-  bool staged = !witness_on_device && !is_group(ctx) && it->second.log_n >= 18;
-  {
-    const char* v = knob("BP_PROVE_STAGED");
-    if (v && *v == '0') staged = false;
-    if (v && *v == '1') staged = !witness_on_device && !is_group(ctx);
-  }
-  if (staged) {
+  // a host witness may be staged by round 1 itself, its uploads beside the commitments (prover_host.hpp, prove_paths)
+  if (prove_paths_of(ctx, it->second, !witness_on_device).staged) {
     const ProveStaged hw = {{a, b, c, public_input}, scalar_fmt};
     return prove_run(ctx, srs_handle, it->second, wit, blind, proof, public_input == nullptr, &hw);
   }
@@ -151,6 +133,8 @@ int bp_prove_last_stats(bp_ctx* ctx, float round_ms[5], float* total_ms) {
 }
 int bp_transcript_test_vector(uint8_t out32[32]) {
   if (!out32) return BP_ERR_INVALID_ARG;
-  transcript_test_vector(out32);
+  MerlinTranscript t("test protocol");                      // merlin's published conformance vector
+  t.append_message("some label", (const uint8_t*)"some data", 9);
+  t.challenge_bytes("challenge", out32, 32);
   return BP_OK;
 }

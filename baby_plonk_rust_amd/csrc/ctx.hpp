@@ -11,6 +11,7 @@
 #include "../../include/bp_msm_ntt.h"
 #include "g1.hpp"
 #include "g1_28.hpp"
+#include "prover_host.hpp"
 
 namespace bp {
 
@@ -81,7 +82,7 @@ struct CircuitEntry {
   fr_t* roots = nullptr;      // w_n^i, i < n (roots_of_unity(group_order), prover.rs:282)
   fr_t* g_pow = nullptr;      // g^i, i < n + 8
   fr_t* ginv_pow = nullptr;   // g^-i, i < 4n
-  fr_t zh_inv[4];             // 1 / (X^n - 1) on the coset (period 4)
+  CosetConsts cc;             // g, w_4n, the four s_j, 1 / (X^n - 1) on the coset ...: computed once, in circuit_build (prover_host.hpp)
   std::vector<CosetShare> split;       // group contexts only: round 3 by coset over the members (empty otherwise)
 };
 
@@ -347,6 +348,7 @@ int commit_lane_finish(bp_ctx* ctx, int j, const MsmPending& pend, g1_proj* out)
 // pi_zero: the caller passed no public inputs, so the PI column of d_wit is all zero (PI(X) = 0: its transforms are skipped, not computed)
 int prove_run(bp_ctx* ctx, uint64_t srs, const CircuitEntry& cir, const fr_t* d_wit, const fr_t blind[11], uint8_t proof[624], bool pi_zero = false,
               const ProveStaged* staged = nullptr);
-void transcript_test_vector(uint8_t out32[32]);
+// the paths a proof of `cir` on `ctx` takes (prover_host.hpp, prove_paths, under the BP_PROVE_* knobs): bp_prove and prove_run both ask here
+ProvePaths prove_paths_of(const bp_ctx* ctx, const CircuitEntry& cir, bool host_witness);
 
 }  // namespace bp

@@ -4,6 +4,7 @@
 #pragma once
 #include "fields.hpp"
 #include "fr_io.hpp"
+#include "prover_host.hpp"      // QuotientArgs, RecombineArgs: filled on the host, tested there
 
 namespace bp {
 
@@ -70,10 +71,6 @@ __global__ void __launch_bounds__(256) fr_lincomb(LinComb lc, fr_t* __restrict__
 //         + alpha^2 (z - 1) L1 ] / (X^n - 1)
 // wit = a | b | c | z | PI evaluations (5 x N), pre = ql qr qm qo qc s1 s2 s3 L1 evaluations (9 x N), N = 4n;
 // z(w X) is z four places further round the coset (w = w_4n^4); X^n - 1 takes four values (zh_inv[i & 3]).
-struct QuotientArgs {
-  fr_t alpha, alpha2, beta, gamma, beta_k1, beta_k2, one;
-  fr_t zh_inv[4];
-};
 // zshift: how many places further z(w X) sits -- 4 on the whole quotient coset g <w_4n> (w = w_4n^4), 1 on one of its four
 // cosets s_j <w_n> (the coset split of a group context, where N = n and the four zh_inv are that coset's one value)
 __global__ void __launch_bounds__(256) quotient_coset(const fr_t* __restrict__ wit, const fr_t* __restrict__ pre,
@@ -151,7 +148,6 @@ __global__ void __launch_bounds__(256) fr_fold_scale(const fr_t* __restrict__ c,
 // t = sum_m x^(m n) t_m from its residues w_j = t mod (x^n - sigma_j), sigma_j = G i4^j (G = g^n, i4 a primitive fourth root of
 // unity): w_j = sum_m G^m i4^(j m) t_m, so G^m t_m = (1/4) sum_j i4^(-j m) w_j -- a radix-4 butterfly per coefficient index.
 // v[j * n + i] = coefficient i of w_j; scale[m] = G^-m / 4; iinv = i4^-1; out[m * n + i] = coefficient i of t_m.
-struct RecombineArgs { fr_t scale[4], iinv; };
 __global__ void __launch_bounds__(256) coset_recombine(const fr_t* __restrict__ v, size_t n, RecombineArgs a, fr_t* __restrict__ out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

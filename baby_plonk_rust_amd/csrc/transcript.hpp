@@ -10,7 +10,8 @@
 #include <string.h>
 
 #include <string>
-#include <vector>
+
+#include "host_codec.hpp"
 
 namespace bp {
 
@@ -123,6 +124,22 @@ class MerlinTranscript {
 
  private:
   Strobe128 strobe_;
+};
+
+// src/transcript.rs:4-86 (alpha is drawn under the label "z_1", :24; challenges are rejection-sampled until canonical
+// and non-zero and then re-absorbed, :70-82)
+struct PlonkTranscript {
+  MerlinTranscript t{"plonk"};                               // prover.rs:112
+  void point48(const char* label, const uint8_t c[48]) { t.append_message(label, c, 48); }       // a compressed point (transcript.rs:66-69)
+  void scalar(const char* label, const fr_t& v) { uint8_t b[32]; fr_to_bytes(b, v, BP_FR_BYTES_LE); t.append_message(label, b, 32); }
+  fr_t challenge(const char* label) {
+    uint8_t b[32];
+    fr_t v;
+    do t.challenge_bytes(label, b, 32);
+    while (!fr_from_bytes(v, b, BP_FR_BYTES_LE) || big_is_zero(v));
+    t.append_message(label, b, 32);
+    return v;
+  }
 };
 
 }  // namespace bp

@@ -164,7 +164,37 @@ def test_synthetic_circuit_native_vs_oracle_restatement(logn, monkeypatch):
         monkeypatch.setenv("BP_PROVE_SIDE", side)
         assert prover.prove_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), None, blinders) == blob, side
         assert prover.prove_with_blinding(PR.SV(cols[0]), PR.SV(cols[1]), PR.SV(cols[2]), PR.SV([0] * n), blinders) == blob, side
+    if logn == 4:                               # the staged round 1 without the side stream: all five coset transforms in round 3
+        monkeypatch.setenv("BP_PROVE_STAGED", "1")
+        monkeypatch.setenv("BP_PROVE_SIDE", "0")
+        assert prover.prove_with_blinding(PR.SV(cols[0]), PR.SV(cols[1]), PR.SV(cols[2]), None, blinders) == blob
+        assert prover.prove_with_blinding(PR.SV(cols[0]), PR.SV(cols[1]), PR.SV(cols[2]), PR.SV([0] * n), blinders) == blob
     circuit.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("logn", [3, 7])
+def test_round3_by_coset_on_one_device_same_bytes(logn, monkeypatch):
+    """BP_PROVE_COSET_ONE=1, read when the circuit is loaded: one device holds all four coset shares and round 3 runs by coset
+    (four size-n transforms per polynomial, the residues recombined) instead of on the whole quotient coset; with and without a PI
+    column: the default path's bytes"""
+    from tests.test_gpu_prover_rounds import synthetic_circuit
+    n = 1 << logn
+    cols, pk, _ = synthetic_circuit(n, 40 + logn)
+    wit = [PR.SV(c) for c in cols]
+    pkv = {k: PR.SV(v) for k, v in pk.items()}
+    blinders = [random.Random(11).randrange(1, Q) for _ in range(11)]
+    setup = bp.Setup.generate_srs(n + 6, 0x1234567)
+    default = bp.Circuit(pkv)
+    blob = bp.Prover(setup, default).prove_with_blinding(*wit, None, blinders)
+    assert len(blob) == 624
+    default.free()
+    monkeypatch.setenv("BP_PROVE_COSET_ONE", "1")
+    by_coset = bp.Circuit(pkv)
+    prover = bp.Prover(setup, by_coset)
+    assert prover.prove_with_blinding(*wit, None, blinders) == blob
+    assert prover.prove_with_blinding(*wit, PR.SV([0] * n), blinders) == blob
+    by_coset.free()
 
 
 def _circuit_from_rows(wires, selectors, n):

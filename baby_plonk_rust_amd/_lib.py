@@ -89,6 +89,11 @@ SIGNATURES = {
     "bp_verify_reduce_segments": (_int, [_vp, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _int, _sz, _vp, _pp(_sz)]),
     "bp_verify_last_stats": (_int, [_vp, _vp]),
     "bp_verify_segments_last_stats": (_int, [_vp, _vp]),
+    "bp_g2_mul_generator": (_int, [_vp, _vp]),
+    "bp_pairing_gt_host": (_int, [_vp, _vp, _vp]),
+    "bp_pairing_check_host": (_int, [_vp, _vp, _sz, _u32, _vp, _vp, _pp(_sz)]),
+    "bp_pairing_check": (_int, [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _pp(_sz)]),
+    "bp_pairing_last_stats": (_int, [_vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

@@ -433,6 +433,16 @@ class Context:
         self.check(self._lib.bp_verify_segments_last_stats(self._h, ms), "bp_verify_segments_last_stats")
         return dict(zip(("mul_ms", "reduce_ms", "encode_ms"), [float(v) for v in ms]))
 
+    def pairing_check(self, pairs, x_2, checks=0, gt=False):
+        """bp_pairing_check: one pairing check per GPU lane; see the module function pairing_check"""
+        return _pairing_check(self, pairs, x_2, checks, gt)
+
+    def pairing_stats(self):
+        """milliseconds of the three stages of the last pairing_check on this context"""
+        ms = (C.c_float * 3)()
+        self.check(self._lib.bp_pairing_last_stats(self._h, ms), "bp_pairing_last_stats")
+        return dict(zip(("prepare_upload_ms", "miller_ms", "final_exp_ms"), [float(v) for v in ms]))
+
     def set_stream(self, stream_ptr):
         self.check(self._lib.bp_set_stream(self._h, stream_ptr), "bp_set_stream")
 
@@ -480,6 +490,69 @@ def bytes96_to_partial(b96):
     if rc != 0:
         raise BpError(rc, "bp_g1_bytes96_to_partial")
     return bytes(out)
+
+
+def g2_mul_generator(k_int):
+    """host-side: k * G2 as 192 bytes (G2Affine::to_uncompressed); x_2 of a setup is g2_mul_generator(tau) (setup.rs:20)"""
+    out = np.zeros(192, dtype=np.uint8)
+    if not 0 <= k_int < 1 << 256:
+        raise BpError(-4, "bp_g2_mul_generator", "scalar outside 0 .. 2^256")
+    k = np.frombuffer(int(k_int).to_bytes(32, "little"), dtype=np.uint8).copy()
+    rc = _lib.load().bp_g2_mul_generator(k.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise BpError(rc, "bp_g2_mul_generator")
+    return bytes(out)
+
+
+def pairing_gt(p96, q192):
+    """host-side: bls12_381::pairing(p, q) as the 576-byte memory image of Gt"""
+    p, q = np.frombuffer(bytes(p96), dtype=np.uint8).copy(), np.frombuffer(bytes(q192), dtype=np.uint8).copy()
+    if len(p) != 96 or len(q) != 192:
+        raise BpError(-6, "bp_pairing_gt_host", "96 and 192 bytes expected")
+    out = np.zeros(576, dtype=np.uint8)
+    rc = _lib.load().bp_pairing_gt_host(p.ctypes.data, q.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise BpError(rc, "bp_pairing_gt_host")
+    return bytes(out)
+
+
+def _pairing_check(ctx, pairs, x_2, checks, gt):
+    """ctx None: bp_pairing_check_host; else bp_pairing_check on that context"""
+    if isinstance(pairs, (list, tuple)):
+        pairs = b"".join(bytes(a) + bytes(b) for a, b in pairs)
+    rec = np.frombuffer(bytes(pairs), dtype=np.uint8).copy()
+    x2 = None if x_2 is None else np.frombuffer(bytes(x_2), dtype=np.uint8).copy()
+    if len(rec) % 192 or x2 is None or len(x2) != 192:
+        raise BpError(-6 if x2 is not None else -1, "pairing_check", "pairs: n x 192 bytes and x_2: 192 bytes expected")
+    n = len(rec) // 192
+    verdicts = np.zeros(max(n, 1), dtype=np.uint8)
+    images = np.zeros(max(n, 1) * 576, dtype=np.uint8) if gt else None
+    bad = C.c_size_t()
+    args = (x2.ctypes.data, rec.ctypes.data if n else None, n, checks, verdicts.ctypes.data, None if images is None else images.ctypes.data, C.byref(bad))
+    lib = _lib.load()
+    rc = lib.bp_pairing_check_host(*args) if ctx is None else ctx._lib.bp_pairing_check(ctx._h, *args)
+    if rc != 0:
+        try:
+            if ctx is None:
+                raise BpError(rc, "bp_pairing_check_host")
+            ctx.check(rc, "bp_pairing_check")
+        except BpError as e:
+            e.index = bad.value if rc == -3 and bad.value != C.c_size_t(-1).value else None
+            raise
+    out = [bool(v) for v in verdicts[:n]]
+    if gt:
+        raw = images.tobytes()
+        return out, [raw[576 * i: 576 * i + 576] for i in range(n)]
+    return out
+
+
+def pairing_check(pairs, x_2, ctx=None, host=False, checks=0, gt=False):
+    """n pairing checks against one setup: verdict i is pairing(A_i, x_2) == pairing(B_i, G2 generator).  pairs: n x 192 bytes
+    A | B (what Verifier.pairing_inputs(_segments) returns, or a list of such pairs); x_2: 192 bytes.  host=True runs on the CPU
+    (bp_pairing_check_host, no context needed), else one check per GPU lane on ctx (default: the default context).  checks: 1 adds
+    the G1 subgroup test, 2 the G2 subgroup test of x_2.  gt=True returns (verdicts, images): the 576-byte Gt image per pair.
+    A rejected point raises BpError with the lowest failing pair in `index`."""
+    return _pairing_check(None if host else (ctx or default_context()), pairs, x_2, checks, gt)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -762,12 +835,16 @@ def round_2_z(a, b, c, s1, s2, s3, beta, gamma, k1=None, k2=None, ctx=None):
 
 
 class Setup:
-    """src/setup.rs:7-10 (G1 part; x_2 in G2 belongs to the verifier's pairing, out of scope).
+    """src/setup.rs:7-10: the powers of tau in G1, resident on the GPU, and x_2 = tau * G2 as 192 bytes (None when the setup was
+    loaded from G1 points alone and no x_2= was given: the verdict methods of Verifier then raise).
     A Setup serves every commitment of a prover, so it builds the SRS's fixed-base window tables once
     (bp_srs_precompute) unless tables=False or BP_SRS_TABLES=0."""
 
-    def __init__(self, handle, ctx, tables=True):
+    def __init__(self, handle, ctx, tables=True, x_2=None):
         self.handle, self.ctx, self.tables_error = handle, ctx, None
+        self.x_2 = None if x_2 is None else bytes(x_2)
+        if self.x_2 is not None and len(self.x_2) != 192:
+            raise BpError(-6, "Setup", "x_2: 192 bytes expected")
         if tables and os.environ.get("BP_SRS_TABLES", "1") != "0":
             try:
                 ctx.srs_precompute(handle, 0)
@@ -778,18 +855,18 @@ class Setup:
     def generate_srs(powers, tau_int, ctx=None, tables=True):
         """setup.rs:12-31: [G, tau G, ..., tau^(powers-1) G], generated and kept on the GPU"""
         ctx = ctx or default_context()
-        return Setup(ctx.srs_generate(powers, tau_int), ctx, tables)
+        return Setup(ctx.srs_generate(powers, tau_int), ctx, tables, g2_mul_generator(tau_int % Q))
 
     @staticmethod
-    def from_points(points96, ctx=None, tables=True):
+    def from_points(points96, ctx=None, tables=True, x_2=None):
         ctx = ctx or default_context()
-        return Setup(ctx.srs_load(points96), ctx, tables)
+        return Setup(ctx.srs_load(points96), ctx, tables, x_2)
 
     @staticmethod
-    def from_compressed(points48, ctx=None, tables=True, check_subgroup=True):
+    def from_compressed(points48, ctx=None, tables=True, check_subgroup=True, x_2=None):
         """a ceremony's SRS: 48-byte compressed records, decoded (and by default subgroup-checked) on the GPU"""
         ctx = ctx or default_context()
-        return Setup(ctx.srs_load_compressed48(points48, check_subgroup), ctx, tables)
+        return Setup(ctx.srs_load_compressed48(points48, check_subgroup), ctx, tables, x_2)
 
     def powers_of_x(self):
         return self.ctx.srs_export(self.handle)
@@ -926,12 +1003,15 @@ def plonk_challenges(proofs, fmt=FR_MONT):
 
 class Verifier:
     """src/verifier.rs:41-79: the verifier's preprocessed input (the eight commitments of Circuit.commitments) for a batch of
-    proofs of that circuit.  The G2 side (x_2) and the pairings stay with the host: pairing_inputs returns the two G1 points
-    (A, B) with  batch valid  <=>  pairing(A, x_2) == pairing(B, G2Affine::generator())  (verifier.rs:187-191)."""
+    proofs of that circuit.  pairing_inputs returns the two G1 points (A, B) with  batch valid  <=>  pairing(A, x_2) ==
+    pairing(B, G2Affine::generator())  (verifier.rs:187-191); verify, verify_each and locate_invalid(decide=None) go on to the
+    verdict with the setup's x_2.  Which path computes the pairings is decided by the method called: verify and locate_invalid
+    use the host (a batch is two pairings: CPU work), verify_each the GPU (one check per lane)."""
 
     def __init__(self, setup, circuit):
         assert setup.ctx is circuit.ctx
         self.ctx, self.group_order = setup.ctx, circuit.group_order
+        self.x_2 = setup.x_2
         self.commitments = circuit.commitments(setup)
         self.vk = b"".join(self.commitments[k] for k in CIRCUIT_COLUMNS)
 
@@ -945,12 +1025,33 @@ class Verifier:
         (weights may be None only with segment=1)"""
         return self.ctx.verify_reduce_segments(self.group_order.bit_length() - 1, self.vk, proofs, public_inputs, weights, challenges, fmt, segment)
 
-    def locate_invalid(self, proofs, public_inputs, weights, decide, fmt=FR_MONT):
-        """the sorted indices of the proofs of a batch whose own pair fails decide(A96, B96) -> bool, the host's pairing check
-        (pairing(A, x_2) == pairing(B, G2 generator)); the library computes no pairing.  ONE GPU call with segment=1 gives a pair
+    def _need_x_2(self, what):
+        if self.x_2 is None:
+            raise BpError(-1, what, "the setup has no x_2 (pass x_2= to Setup.from_points / from_compressed)")
+        return self.x_2
+
+    def verify(self, proofs, public_inputs, weights=None, challenges=None, fmt=FR_MONT):
+        """Verifier::verify (verifier.rs:80-192) of the batch, to the end: pairing_inputs, then the pairing check on the host"""
+        x_2 = self._need_x_2("Verifier.verify")
+        return pairing_check([self.pairing_inputs(proofs, public_inputs, weights, challenges, fmt)], x_2, host=True)[0]
+
+    def verify_each(self, proofs, public_inputs, challenges=None, fmt=FR_MONT):
+        """one verdict per proof: one pair per proof (segment = 1, weight 1), then one pairing check per GPU lane"""
+        x_2 = self._need_x_2("Verifier.verify_each")
+        return pairing_check(self.pairing_inputs_segments(proofs, public_inputs, None, challenges, fmt, 1), x_2, ctx=self.ctx)
+
+    def locate_invalid(self, proofs, public_inputs, weights, decide=None, fmt=FR_MONT):
+        """the sorted indices of the proofs of a batch whose own pair fails decide(A96, B96) -> bool, a pairing check
+        (pairing(A, x_2) == pairing(B, G2 generator)); decide=None: the host pairing check against the setup's x_2.
+        ONE GPU call with segment=1 gives a pair
         per proof; a range's pair is the host sum of its leaves (bp_g1_sum_partials over 144-byte partials), and the search
         descends only into ranges whose sum fails: at most 1 + 2 k ceil(log2 m) decide calls for k bad proofs, 1 for a good batch.
         weights: as pairing_inputs -- they make the sums sound (a failing range may not hide behind cancelling terms)."""
+        if decide is None:
+            x_2 = self._need_x_2("Verifier.locate_invalid")
+
+            def decide(a96, b96):
+                return pairing_check([(a96, b96)], x_2, host=True)[0]
         leaves = self.pairing_inputs_segments(proofs, public_inputs, weights, None, fmt, 1)
         m = len(leaves)
         part_a = b"".join(bytes96_to_partial(a) for a, _ in leaves)

@@ -133,6 +133,9 @@ struct bp_ctx {
   // segment tree and shared bases | normalisation and encoding)
   hipEvent_t verify_seg_ev[2] = {nullptr, nullptr};
   float verify_seg_ms[3] = {0, 0, 0};
+  // bp_pairing_check: the four boundaries of its three stages (prepare + upload + decode | Miller loops | final exponentiations)
+  hipEvent_t pairing_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float pairing_ms[3] = {0, 0, 0};
   std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
   hipEvent_t seam_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // bp_msm_g1_projective144: piece k uploaded and normalised (recorded on the side stream)
   hipStream_t stream = nullptr;

@@ -473,6 +473,39 @@ int  bp_verify_last_stats(bp_ctx* ctx, float stage_ms[5]);
  * the shared bases; normalisation and encoding. */
 int  bp_verify_segments_last_stats(bp_ctx* ctx, float split_ms[3]);
 
+/* ---- pairing checks: from the pairs of bp_verify_reduce(_segments) to verdicts (verifier.rs:187-191) ----
+ * A G2 point is 192 bytes, G2Affine::to_uncompressed (g2.rs:284-303): x.c1 | x.c0 | y.c1 | y.c0, 48 big-endian bytes each, the flag
+ * bits of the G1 encoding in the top of byte 0 (the identity is 0x40 and zeros).  A Gt element is 576 bytes, the memory image of Gt:
+ * twelve Fp of six little-endian u64 Montgomery limbs, in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 -- so that two
+ * implementations can be compared exactly, as with the 144-byte G1Projective image.
+ *
+ * The three calls below are host code and take no context (like bp_plonk_challenges). */
+/* x_2 = k * G2 (setup.rs:20) for a canonical little-endian k; k >= q: BP_ERR_BAD_SCALAR; k = 0 gives the identity encoding. */
+int  bp_g2_mul_generator(const uint8_t k32[32], uint8_t out192[192]);
+/* bls12_381::pairing(p, q) of a G1 point (96 bytes) and a G2 point (192 bytes), both checked for canonical coordinates, flags and
+ * the curve (not the subgroup): BP_ERR_BAD_POINT otherwise.  An identity on either side gives one. */
+int  bp_pairing_gt_host(const uint8_t p96[96], const uint8_t q192[192], uint8_t gt576[576]);
+/* n pairing checks against one setup.  pairs192 is n records A | B of 96 bytes each, exactly what bp_verify_reduce(_segments)
+ * writes; verdicts[i] = 1 iff MillerLoop((A_i, x_2), (-B_i, G2)).final_exponentiation() == 1, i.e. pairing(A_i, x_2) ==
+ * pairing(B_i, G2), else 0.  An identity G1 point drops its term, as multi_miller_loop does (pairings.rs:554-606): (identity,
+ * identity) -- the pair of a weight-0 segment -- gives 1; (identity, B != 0) and (A != 0, identity) give 0.  gt576_or_null, when
+ * not NULL, receives n x 576 bytes: the product after the final exponentiation.
+ * Checks: every G1 point for canonical coordinates, flags and the curve; `checks & 1` adds the G1 subgroup test (not needed for
+ * pairs of our own reduction), `checks & 2` the G2 subgroup test of x_2, which is always decoded and curve-checked.  A rejected G1
+ * point is BP_ERR_BAD_POINT with the LOWEST failing pair index in *first_bad; a rejected x_2 is BP_ERR_BAD_POINT with *first_bad =
+ * SIZE_MAX; an identity x_2 (tau = 0 is not a setup) and a NULL pointer are BP_ERR_INVALID_ARG.  Any rejection leaves verdicts and
+ * gt untouched.  On success *first_bad = SIZE_MAX.  n == 0: BP_OK, verdicts and gt not written (and may be NULL). */
+int  bp_pairing_check_host(const uint8_t x2_192[192], const uint8_t* pairs192, size_t n, uint32_t checks,
+                           uint8_t* verdicts, uint8_t* gt576_or_null, size_t* first_bad);
+/* The same on the GPU, one check per lane: same arguments, same rules, same bytes.  All G2 work (x_2's checks, the prepared lines
+ * of x_2 and of the generator) is host work done once per call.  Blocking; ordered on the context's stream; a bp_init_multi
+ * context runs on its primary device; buffers are workspaces of the context (a second call of the same size allocates nothing). */
+int  bp_pairing_check(bp_ctx* ctx, const uint8_t x2_192[192], const uint8_t* pairs192, size_t n, uint32_t checks,
+                      uint8_t* verdicts, uint8_t* gt576_or_null, size_t* first_bad);
+/* Milliseconds of the stages of the last bp_pairing_check: preparing the lines, upload and decoding; the Miller loops; the final
+ * exponentiations (all 0 after an empty call). */
+int  bp_pairing_last_stats(bp_ctx* ctx, float stage_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

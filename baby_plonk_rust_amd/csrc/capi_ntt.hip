@@ -93,12 +93,10 @@ static int ntt_columns_over_members(bp_ctx* ctx, uint8_t* data, uint32_t log_n, 
 // Returns 1 (not an error code of the ABI) when the shape does not split; only then does the caller run the transform on the
 // leader.  Any other failure is returned as it is: the download phase writes `data` from every member at once, so after a
 // failed copy the buffer may be part input, part output, and must not be transformed again.
-static int ntt_one_over_members(bp_ctx* ctx, uint8_t* data, uint32_t log_n, int inverse, int scalar_fmt) {
+static int ntt_one_over_members(bp_ctx* ctx, const NttHostPlan& plan, uint8_t* data, int inverse, int scalar_fmt) {
   const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const uint32_t R = (uint32_t)sh.size();
-  if (!ntt_split_ok(log_n, R)) return 1;
-  uint32_t l1 = 0;
-  ntt_split_shape(log_n, &l1);
+  const uint32_t R = (uint32_t)sh.size(), log_n = plan.dev.k, l1 = plan.dev.l[0];
+  if (!ntt_split_ok(plan, R)) return 1;
   const size_t N = (size_t)1 << log_n, S = (size_t)1 << (log_n - l1), L1 = (size_t)1 << l1;     // rows of pass 1 x row length
   const size_t cols = S / R, rows = L1 / R, esz = sizeof(fr_t);
   std::vector<fr_t*> dbuf(R, nullptr), tbuf(R, nullptr);
@@ -121,7 +119,7 @@ static int ntt_one_over_members(bp_ctx* ctx, uint8_t* data, uint32_t log_n, int 
     hipError_t e = hipMemcpy2DAsync(dbuf[g] + g * cols, S * esz, data + g * cols * esz, S * esz, cols * esz, L1, hipMemcpyHostToDevice, m->stream);
     if (e != hipSuccess) return fail(m, BP_ERR_HIP, "NTT column-slice upload", e, __FILE__, __LINE__);
     if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(m, dbuf[g], N, 0));      // other columns: unused memory, converted and ignored
-    BP_TRY(ntt_run_part(m, dbuf[g], log_n, inverse, 1, N, 0, g, R));
+    BP_TRY(ntt_run_part(m, plan, dbuf[g], inverse, 1, N, 0, g, R));
     BP_HIP(m, hipEventRecord(m->ev[4], m->stream));               // pass 1 of this member is behind this event: the exchange waits for it
     BP_HIP(m, stream_wait(m->stream));
     return BP_OK;
@@ -138,7 +136,7 @@ static int ntt_one_over_members(bp_ctx* ctx, uint8_t* data, uint32_t log_n, int 
       if (e == hipSuccess) e = hipMemcpy2DAsync(tbuf[to] + off, S * esz, tbuf[from] + off, S * esz, cols * esz, rows, hipMemcpyDefault, m->stream);   // the runtime finds the two devices
       if (e != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "NTT block exchange", e, __FILE__, __LINE__);
     }
-    if (rc == BP_OK) rc = lift(ctx, m, ntt_run_part(m, dbuf[to], log_n, inverse, 1, N, 1, to, R));
+    if (rc == BP_OK) rc = lift(ctx, m, ntt_run_part(m, plan, dbuf[to], inverse, 1, N, 1, to, R));
     if (rc == BP_OK && scalar_fmt == BP_FR_BYTES_LE) rc = lift(ctx, m, fr_convert_run(m, dbuf[to], N, 1));
   }
   for (uint32_t g = 0; g < R; g++) {                           // every member, also after a failure elsewhere
@@ -177,8 +175,10 @@ int bp_ntt_fr(bp_ctx* ctx, void* data, uint32_t log_n, int inverse, int scalar_f
   if (batch > 1 && stride < N) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NTT stride < N");
   if (batch > 65535) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "NTT batch > 65535");
   if (is_group(ctx) && batch > 1) return ntt_columns_over_members(ctx, (uint8_t*)data, log_n, inverse, scalar_fmt, batch, stride);
-  if (is_group(ctx) && log_n >= knob_u32("BP_NTT_GROUP_SPLIT_FROM", 22, 11, 29)) {     // one large transform: every member's PCIe link and a share of the work
-    const int rc = ntt_one_over_members(ctx, (uint8_t*)data, log_n, inverse, scalar_fmt);
+  const NttKnobs knobs = ntt_knobs();
+  const NttHostPlan plan = ntt_plan(log_n, knobs);            // the one plan of this call
+  if (is_group(ctx) && log_n >= knobs.group_split_from) {     // one large transform: every member's PCIe link and a share of the work
+    const int rc = ntt_one_over_members(ctx, plan, (uint8_t*)data, inverse, scalar_fmt);
     if (rc != 1) return rc;                 // done, or a real failure (reported, never papered over: host data may be partly written);
   }                                         // 1 = the shape does not split over this many members: on the leader
   DeviceGuard guard(ctx->device);
@@ -193,7 +193,7 @@ int bp_ntt_fr(bp_ctx* ctx, void* data, uint32_t log_n, int inverse, int scalar_f
     BP_TRY(fr_convert_run(ctx, d, span, 0));
   } else
     BP_TRY(upload_fr(ctx, "io.ntt", data, span, span, scalar_fmt, &d, bad));
-  BP_TRY(ntt_run(ctx, d, log_n, inverse, batch, stride));
+  BP_TRY(ntt_run_part(ctx, plan, d, inverse, batch, stride, -1, 0, 1));
   BP_TRY(download_fr(ctx, d, data, span, scalar_fmt, bad));
   BP_HIP(ctx, hipEventElapsedTime(&ctx->ntt_ms, ctx->ev[0], ctx->ev[1]));
   return BP_OK;

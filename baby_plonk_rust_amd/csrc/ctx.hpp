@@ -11,6 +11,7 @@
 #include "../../include/bp_msm_ntt.h"
 #include "g1.hpp"
 #include "g1_28.hpp"
+#include "ntt_plan.hpp"
 #include "prover_host.hpp"
 
 namespace bp {
@@ -298,11 +299,11 @@ int srs_to28_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28** d_o
 int srs_to28_into(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28* d_out);      // the same into a buffer of the caller's, on ctx->stream
 int ntt_init_tables(bp_ctx* ctx);
 int ntt_run(bp_ctx* ctx, fr_t* d_data, uint32_t log_n, int inverse, size_t batch, size_t stride);
-// one transform in two phases over the members of a group context (ntt.hip)
-bool ntt_split_ok(uint32_t log_n, uint32_t parts);
-void ntt_split_shape(uint32_t log_n, uint32_t* l1);
+// one transform in two phases over the members of a group context (ntt.hip): the caller makes the plan once, ntt_plan(log_n, ntt_knobs()),
+// asks ntt_split_ok(plan, parts) and hands the same plan to every part
+NttKnobs ntt_knobs();
 int ntt_tmp_buffer(bp_ctx* ctx, uint32_t log_n, fr_t** out);
-int ntt_run_part(bp_ctx* ctx, fr_t* d_data, uint32_t log_n, int inverse, size_t batch, size_t stride, int phase, uint32_t part, uint32_t parts);
+int ntt_run_part(bp_ctx* ctx, const NttHostPlan& plan, fr_t* d_data, int inverse, size_t batch, size_t stride, int phase, uint32_t part, uint32_t parts);
 // d_bad (dir 0 only): device word raised to 1 when an input is >= q (Scalar::from_bytes rejects it, scalar.rs:264-288); nullptr = unchecked
 int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir, uint32_t* d_bad = nullptr);
 // the same test without the conversion; row != 0: the n elements lie in rows of `row`, row b at d + b * stride

@@ -18,25 +18,11 @@
 #pragma once
 #include "fr_io.hpp"
 #include "fr29.hpp"
+#include "ntt_plan.hpp"      // tile layout (ntt_tile_pitch / _stride / _tw_off, tile_at), kernel limits, NttPlan
 
 namespace bp {
 
-constexpr int NTT_MAX_PASS_LOG = 10;    // per-pass transform length up to 2^10
-constexpr int NTT_SMALL_MAX_LOG = 10;   // single-workgroup transform up to 2^10
-// tile columns C = 2^cl shrink as the per-pass length grows so that TWO tiles (2^l x (C+1) x 36 B each, plus stage twiddles)
-// fit the 160 KiB of LDS wherever possible: with one 1 024-lane workgroup per CU nothing overlaps a tile's global loads and
-// stores, with two the other one computes meanwhile (measured, profiles/r02_ntt_tile_width_ab.txt: l = 8: C = 8 -> 4 is -8 %
-// at 2^22 and 2^24; l = 9: C = 4 -> 2 is -25 % at 2^18).  l <= 7 -> C = 8 (256-B global runs), l = 8 -> 4, l = 9 -> 2,
-// l = 10 -> 2 (one tile per CU: a single column would halve the run to 32 B and measured +32 %)
-__host__ __device__ constexpr uint32_t ntt_tile_cols_log(uint32_t l) { return l <= 7 ? 3u : (l == 8 ? 2u : 1u); }
-
-struct NttPlan {
-  uint32_t k;            // log2 N
-  uint32_t P;            // passes
-  uint32_t l[4];         // digit widths
-  uint32_t cl[4];        // log2 of the tile's column count per pass (ntt_tile_cols_log unless overridden)
-  uint32_t h;            // low table has 2^h entries, high table 2^(k-h)
-};
+static_assert(NTT_LIMBS == (uint32_t)N29, "the LDS layout of ntt_plan.hpp counts fr29 limbs");
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32 - bits) : 0; }
 
@@ -111,26 +97,6 @@ __device__ __forceinline__ void fr29_butterfly_notwiddle(fr29& u, fr29& v) {
   for (int i = 0; i < N29; i++) v.l[i] = borrow ? d2.l[i] : d.l[i];
   u = s;
 }
-
-// Tile addressing, element (row, c) of a tile of 2^l rows x C columns:
-//   padded   (SWZ = false): row * CP + c with CP = C + 1 (a single column needs no pad);
-//   swizzled (SWZ = true, C = 8 and l <= 7 only): no pad -- ((row ^ z(row)) << 3) | c, where z puts the parity of row bits
-//            2, 4, 6 into bit 0 and the parity of bits 3, 5 into bit 1.  Every access pattern of a pass (the fill: consecutive
-//            rows; a stage: rows j, j + 1, .. of one block, or -- last stage pairs -- rows 4 or 8 apart; the drain: rows in
-//            bit-reversed order, i.e. 64, 32, 96 apart) then spreads the 8-element groups of the lanes of one LDS cycle over
-//            different banks, which the one-element pad does not do for the drain (row pitch 72 B: rows 16 apart collide).
-//            Without the pad a 2^7 x 8 tile plus its stage twiddles is 39 KiB (four would fit a CU; the butterflies' 129 registers
-//            allow three workgroups = three waves per SIMD, and tools/ntt_occupancy_probe.sh shows the pass time does not depend on
-//            the residency: T = 10 us + 11 us per tile per CU with one, three or four resident -- the VALU is the bound).
-template <bool SWZ>
-__device__ __forceinline__ uint32_t tile_at(uint32_t row, uint32_t c, uint32_t CP) {
-  if (SWZ) {
-    const uint32_t z = (__popc(row & 0x54u) & 1u) | ((__popc(row & 0x28u) & 1u) << 1);
-    return ((row ^ z) << 3) | c;
-  }
-  return row * CP + c;
-}
-__host__ __device__ constexpr uint32_t ntt_tw_slots(uint32_t l) { return (1u << l) < 4 ? 2u : (1u << l) >> 1; }
 
 // In-LDS radix-2 decimation-in-frequency transform of length L = 2^l on every column of a tile (C = 2^cl live columns).
 // Result of output index e sits at row bitrev(e).
@@ -240,16 +206,17 @@ __device__ __forceinline__ void lds_ntt_dif(uint32_t* tile, uint32_t tstride, co
 
 // Single-pass transform: N = 2^k <= 2^10, one workgroup per transform (blockIdx.x = batch index).
 // small_tw[j] = w_1024^j (forward or inverse table), scale = N^-1 as a twiddle record, or null.
-__global__ void __launch_bounds__(256) ntt_small(fr_t* __restrict__ data, size_t stride, uint32_t k,
+__global__ void __launch_bounds__(NTT_SMALL_THREADS) ntt_small(fr_t* __restrict__ data, size_t stride, uint32_t k,
                                                   const tw29_t* __restrict__ small_tw, const tw29_t* scale) {
-  const uint32_t N = 1u << k, tstride = (N + 1) & ~1u;
+  constexpr uint32_t CP = ntt_tile_pitch(1);        // one column
+  const uint32_t N = 1u << k, tstride = ntt_tile_stride(N * CP);
   uint32_t* tile = ntt_lds_raw;
-  uint32_t* tw = tile + N29 * tstride;
+  uint32_t* tw = tile + ntt_tile_tw_off(tstride);
   fr_t* base = data + (size_t)blockIdx.x * stride;
   for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) lds_st29(tile, tstride, i, fr29_from_sat(load_fr(&base[i])));
   lds_fill_stage_twiddles(tw, k, small_tw);
   __syncthreads();
-  lds_ntt_dif<false>(tile, tstride, tw, small_tw, k, 0, 1);
+  lds_ntt_dif<false>(tile, tstride, tw, small_tw, k, 0, CP);
   fr29 sc;
   if (scale) sc = load_tw29(scale);
   for (uint32_t e = threadIdx.x; e < N; e += blockDim.x) {
@@ -319,11 +286,11 @@ __device__ __forceinline__ void ntt_pass_strided_body(const NttStridedArgs& a) {
   const fr_t* src = a.src;
   const tw29_t* __restrict__ small_tw = a.small_tw;
   const uint32_t k = a.k, l = a.l, s = a.s, cl = a.cl;
-  const uint32_t C = 1u << cl, CP = SWZ || C == 1 ? C : C + 1;        // a single column needs no row pad
+  const uint32_t C = 1u << cl, CP = SWZ ? C : ntt_tile_pitch(C);
   const uint32_t bx = blockIdx.x + a.tile0;
-  const uint32_t L = 1u << l, mlog = l + s, tstride = (L * CP + 1) & ~1u;      // even: the limb-pair arrays stay 8-byte aligned
+  const uint32_t L = 1u << l, mlog = l + s, tstride = ntt_tile_stride(L * CP);
   uint32_t* tile = ntt_lds_raw;
-  uint32_t* tw = tile + N29 * tstride;
+  uint32_t* tw = tile + ntt_tile_tw_off(tstride);
   const uint32_t tiles_per_hi = 1u << (s - cl);
   const uint32_t hi = bx / tiles_per_hi, r0 = (bx % tiles_per_hi) << cl;
   {
@@ -376,9 +343,9 @@ __device__ __forceinline__ void ntt_pass_strided_body(const NttStridedArgs& a) {
     store_fr(&dst[doff + base + ((size_t)e << s) + c], fr29_pack(v));
   }
 }
-__global__ void __launch_bounds__(512) ntt_pass_strided(NttStridedArgs a) { ntt_pass_strided_body<false>(a); }
+__global__ void __launch_bounds__(NTT_PAD_THREADS) ntt_pass_strided(NttStridedArgs a) { ntt_pass_strided_body<false>(a); }
 // 2^l x 8 tiles, l <= 7, unpadded with swizzled rows: 256 lanes, three workgroups per CU
-__global__ void __launch_bounds__(256, 3) ntt_pass_strided_swz(NttStridedArgs a) { ntt_pass_strided_body<true>(a); }
+__global__ void __launch_bounds__(NTT_SWZ_THREADS, NTT_SWZ_PER_CU) ntt_pass_strided_swz(NttStridedArgs a) { ntt_pass_strided_body<true>(a); }
 
 // Last pass: contiguous rows of length L = 2^l (l = l_P); tile = C rows with consecutive e_1.
 // Row (e_1, mid): src address (e_1 * 2^(s1 - l) + mid) * L + d, s1 = k - l_1.
@@ -399,9 +366,9 @@ __device__ __forceinline__ void ntt_pass_last_body(const NttLastArgs& a) {
   const fr_t* __restrict__ src = a.src;
   const tw29_t* __restrict__ small_tw = a.small_tw;
   const uint32_t k = a.plan.k, P = a.plan.P, l = a.plan.l[P - 1], l1 = a.plan.l[0], L = 1u << l, bx = blockIdx.x + a.tile0;
-  const uint32_t cl = a.plan.cl[P - 1], C = 1u << cl, CP = SWZ || C == 1 ? C : C + 1, tstride = (L * CP + 1) & ~1u;
+  const uint32_t cl = a.plan.cl[P - 1], C = 1u << cl, CP = SWZ ? C : ntt_tile_pitch(C), tstride = ntt_tile_stride(L * CP);
   uint32_t* tile = ntt_lds_raw;
-  uint32_t* tw = tile + N29 * tstride;
+  uint32_t* tw = tile + ntt_tile_tw_off(tstride);
   const uint32_t midbits = k - l1 - l;              // bits of (e_2 .. e_{P-1})
   // blockIdx.x enumerates (e1_tile, mid): e_1 = e1_tile * C + c
   const uint32_t mid = bx & ((1u << midbits) - 1u), e1_0 = (bx >> midbits) << cl;
@@ -435,87 +402,7 @@ __device__ __forceinline__ void ntt_pass_last_body(const NttLastArgs& a) {
     store_fr(&dst[doff + obase + ((size_t)e << (k - l)) + c], fr29_to_sat_canonical(v));
   }
 }
-__global__ void __launch_bounds__(512) ntt_pass_last(NttLastArgs a) { ntt_pass_last_body<false>(a); }
-__global__ void __launch_bounds__(256, 3) ntt_pass_last_swz(NttLastArgs a) { ntt_pass_last_body<true>(a); }
-
-// ---- element-wise helpers used by the Polynomial layer (src/polynomial.rs) -------------------------
-// op: 0 a+b, 1 a-b, 2 a*b (pointwise), with broadcast of a single scalar when nb == 1 is not done here.
-__global__ void __launch_bounds__(256) fr_binary(const fr_t* a, size_t na, const fr_t* b, size_t nb,
-                                                  fr_t* out, size_t n, int op) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  fr_t x = i < na ? load_fr(&a[i]) : Fr::zero(), y = i < nb ? load_fr(&b[i]) : Fr::zero(), r;
-  if (op == 0) Fr::add(r, x, y);
-  else if (op == 1) Fr::sub(r, x, y);
-  else Fr::mul(r, x, y);
-  store_fr(&out[i], r);
-}
-// out[i] = a[i] (op) s for i < n;  op: 0 add, 1 sub, 2 mul
-__global__ void __launch_bounds__(256) fr_scalar_op(const fr_t* a, fr_t s, fr_t* out, size_t n, int op) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  fr_t x = load_fr(&a[i]), r;
-  if (op == 0) Fr::add(r, x, s);
-  else if (op == 1) Fr::sub(r, x, s);
-  else Fr::mul(r, x, s);
-  store_fr(&out[i], r);
-}
-// Synthetic uniform scalars: element i = from_u512 (scalar.rs:323-339) of eight
-// SplitMix64 outputs of the stream seeded with seed + 8*i*golden; Montgomery limbs out.
-__device__ __forceinline__ uint64_t splitmix64_next(uint64_t& s) {
-  uint64_t z = (s += 0x9e3779b97f4a7c15ull);
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-__global__ void __launch_bounds__(256) fr_synthetic(fr_t* __restrict__ out, size_t n, uint64_t seed) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t st = seed + 0x9e3779b97f4a7c15ull * 8ull * i;
-  fr_t d0, d1, r3;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    uint64_t z = splitmix64_next(st);
-    d0.l[2 * k] = (uint32_t)z;
-    d0.l[2 * k + 1] = (uint32_t)(z >> 32);
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    uint64_t z = splitmix64_next(st);
-    d1.l[2 * k] = (uint32_t)z;
-    d1.l[2 * k + 1] = (uint32_t)(z >> 32);
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) r3.l[k] = FrParams::r3(k);
-  // the Montgomery product needs a*b < q*R only, which holds for any 256-bit a and b < q
-  Fr::mul(d0, d0, Fr::r2());
-  Fr::mul(d1, d1, r3);
-  Fr::add(d0, d0, d1);
-  store_fr(&out[i], d0);
-}
-// in-place conversion between 32-byte LE canonical and Montgomery limbs (dir 0: to Montgomery, 1: from)
-// dir 0 with bad != nullptr: *bad becomes 1 when an input is not canonical (>= q); the caller reads the word with the copy that ends its call
-__device__ __forceinline__ bool fr_is_canonical(const fr_t& x) {
-  fr_t t;
-  return big_sub(t, x, Fr::modulus()) != 0;
-}
-__global__ void __launch_bounds__(256) fr_convert(fr_t* __restrict__ a, size_t n, int dir, uint32_t* __restrict__ bad) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  fr_t x = load_fr(&a[i]), r;
-  if (dir == 0) {
-    if (bad && !fr_is_canonical(x)) atomicMax(bad, 1u);
-    Fr::to_mont(r, x);
-  } else Fr::from_mont(r, x);
-  store_fr(&a[i], r);
-}
-// the same test alone, for canonical vectors that need no conversion (add / sub commute with the Montgomery map) and for rows
-// with unused memory between them: n elements in rows of `row`, row b at a + b * stride
-__global__ void __launch_bounds__(256) fr_flag_noncanonical(const fr_t* __restrict__ a, size_t n, size_t row, size_t stride, uint32_t* __restrict__ bad) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  fr_t x = load_fr(&a[(i / row) * stride + i % row]);
-  if (!fr_is_canonical(x)) atomicMax(bad, 1u);
-}
+__global__ void __launch_bounds__(NTT_PAD_THREADS) ntt_pass_last(NttLastArgs a) { ntt_pass_last_body<false>(a); }
+__global__ void __launch_bounds__(NTT_SWZ_THREADS, NTT_SWZ_PER_CU) ntt_pass_last_swz(NttLastArgs a) { ntt_pass_last_body<true>(a); }
 
 }  // namespace bp

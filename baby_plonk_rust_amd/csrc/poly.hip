@@ -1,4 +1,4 @@
-// poly.hip -- host drivers of the polynomial kernels (poly_kernels.hpp).
+// poly.hip -- host drivers of the polynomial kernels and of the element-wise Fr kernels (poly_kernels.hpp).
 #include <string.h>
 
 #include <algorithm>
@@ -215,6 +215,45 @@ int grand_product_run(bp_ctx* ctx, const fr_t* a, const fr_t* b, const fr_t* c, 
   fr_t td_inv;
   fr_invert(td_inv, h_tot[1]);
   hipLaunchKernelGGL(grand_product_combine, dim3(blocks), dim3(256), 0, ctx->stream, pn, sd, td_inv, n, d_z);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+
+int fr_convert_run(bp_ctx* ctx, fr_t* d, size_t n, int dir, uint32_t* d_bad) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(fr_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, dir, dir == 0 ? d_bad : nullptr);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_flag_noncanonical_run(bp_ctx* ctx, const fr_t* d, size_t n, uint32_t* d_bad, size_t row, size_t stride) {
+  if (n == 0 || !d_bad) return BP_OK;
+  if (row == 0) row = stride = n;
+  hipLaunchKernelGGL(fr_flag_noncanonical, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, n, row, stride, d_bad);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_bad_word(bp_ctx* ctx, int fmt, uint32_t** d_bad) {
+  *d_bad = nullptr;
+  if (fmt != BP_FR_BYTES_LE) return BP_OK;
+  BP_TRY(ws_get(ctx, "io.fr_bad", 16, (void**)d_bad));
+  BP_HIP(ctx, hipMemsetAsync(*d_bad, 0, 4, ctx->stream));
+  return BP_OK;
+}
+int fr_binary_run(bp_ctx* ctx, const fr_t* a, size_t na, const fr_t* b, size_t nb, fr_t* out, size_t n, int op) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(fr_binary, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, na, b, nb, out, n, op);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_scalar_run(bp_ctx* ctx, const fr_t* a, const fr_t& s, fr_t* out, size_t n, int op) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(fr_scalar_op, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, s, out, n, op);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+int fr_synthetic_run(bp_ctx* ctx, fr_t* d_out, size_t n, uint64_t seed) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(fr_synthetic, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_out, n, seed);
   BP_HIP(ctx, hipGetLastError());
   return BP_OK;
 }

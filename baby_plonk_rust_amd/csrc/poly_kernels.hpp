@@ -1,7 +1,7 @@
 // poly_kernels.hpp -- device kernels behind the Polynomial operators of src/polynomial.rs:
 //   evaluation at a point (coeffs_evaluate :34-45), division by a binomial b0 + bm x^m (the only
 //   divisors the prover uses: Z_H = x^n - 1 at prover.rs:450 and x - zeta / x - zeta*omega at :623-638),
-//   and a general long division for everything else.  Element-wise ops live in ntt_kernels.hpp.
+//   and a general long division for everything else; the element-wise Fr kernels at the end.
 #pragma once
 #include "fr_io.hpp"
 
@@ -556,6 +556,86 @@ __global__ void __launch_bounds__(1024) poly_div_general(fr_t* __restrict__ rem,
     }
     __syncthreads();
   }
+}
+
+// ---- element-wise helpers used by the Polynomial layer (src/polynomial.rs) -------------------------
+// op: 0 a+b, 1 a-b, 2 a*b (pointwise), with broadcast of a single scalar when nb == 1 is not done here.
+__global__ void __launch_bounds__(256) fr_binary(const fr_t* a, size_t na, const fr_t* b, size_t nb,
+                                                  fr_t* out, size_t n, int op) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t x = i < na ? load_fr(&a[i]) : Fr::zero(), y = i < nb ? load_fr(&b[i]) : Fr::zero(), r;
+  if (op == 0) Fr::add(r, x, y);
+  else if (op == 1) Fr::sub(r, x, y);
+  else Fr::mul(r, x, y);
+  store_fr(&out[i], r);
+}
+// out[i] = a[i] (op) s for i < n;  op: 0 add, 1 sub, 2 mul
+__global__ void __launch_bounds__(256) fr_scalar_op(const fr_t* a, fr_t s, fr_t* out, size_t n, int op) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t x = load_fr(&a[i]), r;
+  if (op == 0) Fr::add(r, x, s);
+  else if (op == 1) Fr::sub(r, x, s);
+  else Fr::mul(r, x, s);
+  store_fr(&out[i], r);
+}
+// Synthetic uniform scalars: element i = from_u512 (scalar.rs:323-339) of eight
+// SplitMix64 outputs of the stream seeded with seed + 8*i*golden; Montgomery limbs out.
+__device__ __forceinline__ uint64_t splitmix64_next(uint64_t& s) {
+  uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+__global__ void __launch_bounds__(256) fr_synthetic(fr_t* __restrict__ out, size_t n, uint64_t seed) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t st = seed + 0x9e3779b97f4a7c15ull * 8ull * i;
+  fr_t d0, d1, r3;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint64_t z = splitmix64_next(st);
+    d0.l[2 * k] = (uint32_t)z;
+    d0.l[2 * k + 1] = (uint32_t)(z >> 32);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint64_t z = splitmix64_next(st);
+    d1.l[2 * k] = (uint32_t)z;
+    d1.l[2 * k + 1] = (uint32_t)(z >> 32);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) r3.l[k] = FrParams::r3(k);
+  // the Montgomery product needs a*b < q*R only, which holds for any 256-bit a and b < q
+  Fr::mul(d0, d0, Fr::r2());
+  Fr::mul(d1, d1, r3);
+  Fr::add(d0, d0, d1);
+  store_fr(&out[i], d0);
+}
+// in-place conversion between 32-byte LE canonical and Montgomery limbs (dir 0: to Montgomery, 1: from)
+// dir 0 with bad != nullptr: *bad becomes 1 when an input is not canonical (>= q); the caller reads the word with the copy that ends its call
+__device__ __forceinline__ bool fr_is_canonical(const fr_t& x) {
+  fr_t t;
+  return big_sub(t, x, Fr::modulus()) != 0;
+}
+__global__ void __launch_bounds__(256) fr_convert(fr_t* __restrict__ a, size_t n, int dir, uint32_t* __restrict__ bad) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t x = load_fr(&a[i]), r;
+  if (dir == 0) {
+    if (bad && !fr_is_canonical(x)) atomicMax(bad, 1u);
+    Fr::to_mont(r, x);
+  } else Fr::from_mont(r, x);
+  store_fr(&a[i], r);
+}
+// the same test alone, for canonical vectors that need no conversion (add / sub commute with the Montgomery map) and for rows
+// with unused memory between them: n elements in rows of `row`, row b at a + b * stride
+__global__ void __launch_bounds__(256) fr_flag_noncanonical(const fr_t* __restrict__ a, size_t n, size_t row, size_t stride, uint32_t* __restrict__ bad) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t x = load_fr(&a[(i / row) * stride + i % row]);
+  if (!fr_is_canonical(x)) atomicMax(bad, 1u);
 }
 
 }  // namespace bp

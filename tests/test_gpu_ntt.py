@@ -8,7 +8,7 @@ import pytest
 import baby_plonk_rust_amd as bp
 from oracle import oracle as O
 from tests import bigint_model as M
-from tests.gpu_common import NTHREADS, Q
+from tests.gpu_common import NTHREADS, Q, experiment
 
 pytestmark = pytest.mark.gpu
 
@@ -140,6 +140,41 @@ def test_async_transforms_back_to_back(ctx):
     assert st["device_ms"] > 0 and st["passes"] == 2
     ctx.ntt_device(t.data_ptr(), 14, inverse=True)               # a blocking call after enqueued ones
     assert (t.cpu().numpy().view(np.uint64).reshape(-1, 4) == x).all()
+
+
+@experiment
+def test_driver_branches_under_knobs(monkeypatch):
+    """the branches of the driver (csrc/ntt.hip) that no default-size transform reaches, at the smallest sizes that reach them, forward
+    and inverse against the oracle: the two-level lookup drain (by default above 2^24 only), padded 8-column tiles, a single column
+    without pad, two- and three-pass splits of the knob's choosing, the middle-digit swap of (a, a, a - 1), and -- all on ONE context, so
+    that a later knob meets the inter-pass tables an earlier one built -- the rebuild of a pass table whose (l, s) changed.  The shapes
+    themselves are judged on the CPU (tests/test_ntt_plan.py); BP_NTT_LANES_SHIFT and the splits the plan rejects stay there."""
+    ctx = bp.Context(0)                 # its own: the default context's tables for these sizes would outlive BP_NTT_FULL_TWIDDLES_MAX_LOG=0
+    data = {logn: O.splitmix_scalars(1 << logn, 0xD21E00 + logn) for logn in (11, 12, 13)}
+    want = {(logn, inv): O.ntt_fast(a, inverse=inv) for logn, a in data.items() for inv in (False, True)}
+    knobs = ("BP_NTT_FULL_TWIDDLES_MAX_LOG", "BP_NTT_SWIZZLE", "BP_NTT_SPLIT", "BP_NTT_THREE_PASS_FROM", "BP_NTT_COLS_LOG_L7")
+
+    def run(logn, passes, **env):
+        for name in knobs:
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        for inv in (False, True):
+            got = bp.i_ntt_381(data[logn], ctx) if inv else bp.ntt_381(data[logn], ctx)
+            assert (got == want[logn, inv]).all(), (logn, inv, env)
+            assert ctx.ntt_stats()["passes"] == passes, (logn, env)
+
+    run(11, 2, BP_NTT_FULL_TWIDDLES_MAX_LOG="0")       # 6, 5 and 6, 6 with no full table: lo / hi lookup in the drain
+    run(12, 2, BP_NTT_FULL_TWIDDLES_MAX_LOG="0")
+    run(12, 2)                                         # the same split, now through full tables (built here)
+    run(12, 2, BP_NTT_SWIZZLE="0")                     # 2^6 x 8 tiles, padded
+    run(11, 2, BP_NTT_SPLIT="11:9,2,0")
+    run(12, 2, BP_NTT_SPLIT="12:10,2,0")               # (l, s) = (10, 2) where the table holds (6, 6): rebuilt
+    run(13, 3, BP_NTT_SPLIT="13:5,4,4")
+    run(11, 3, BP_NTT_THREE_PASS_FROM="11")            # 4, 4, 3 -> 4, 3, 4; pass 1's table held (9, 2)
+    run(12, 2, BP_NTT_COLS_LOG_L7="0")                 # one column, no pad; back to (6, 6) from (10, 2)
+    run(11, 2)                                         # and the default again, from the three-pass tables
+    ctx.close()
 
 
 # ---- closed-form vectors through the multi-pass kernels ------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""-m gpu: the Polynomial layer (csrc/poly.hip, poly_kernels.hpp, the element-wise kernels of ntt_kernels.hpp, capi_poly.hip) at
+"""-m gpu: the Polynomial layer (csrc/poly.hip, poly_kernels.hpp, capi_poly.hip) at
 the edges of its dispatch: every division path at its thresholds (Context.poly_stats() says which one ran), evaluation across the
 K = 16 -> 32 switch and past 256 partials, products at the single-pass / multi-pass transform edge, the device entry points across
 workgroup edges, with unequal lengths and in place, the grand product past 256 scan tiles, and canonical-byte vectors holding a

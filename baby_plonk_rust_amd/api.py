@@ -186,6 +186,19 @@ class Context:
         self.check(self._lib.bp_srs_export_projective144(self._h, handle, first, n, out.ctypes.data), "bp_srs_export_projective144")
         return out
 
+    def srs_lagrange(self, handle, log_n):
+        """the Lagrange-basis SRS [L_i(tau)] G over the 2^log_n-th roots of unity, from the first 2^log_n points of a powers-of-tau
+        SRS: the inverse NTT taken in G1, on the GPU, tau unknown (bp_srs_lagrange).  Returns a new SRS handle; the source stays"""
+        h = C.c_uint64()
+        self.check(self._lib.bp_srs_lagrange(self._h, handle, log_n, C.byref(h)), "bp_srs_lagrange")
+        return h.value
+
+    def srs_basis(self, handle):
+        """(BASIS_MONOMIAL, 0) for a loaded or generated SRS, (BASIS_LAGRANGE, log_n) for one made by srs_lagrange"""
+        b, k = C.c_int(), C.c_uint32()
+        self.check(self._lib.bp_srs_basis(self._h, handle, C.byref(b), C.byref(k)), "bp_srs_basis")
+        return b.value, k.value
+
     def srs_free(self, handle):
         self.check(self._lib.bp_srs_free(self._h, handle), "bp_srs_free")
 
@@ -874,13 +887,33 @@ class Setup:
     def powers_of_x_compressed(self):
         return self.ctx.srs_export_compressed48(self.handle)
 
+    @property
+    def basis(self):
+        """BASIS_MONOMIAL (powers of tau), or BASIS_LAGRANGE for a Setup made by lagrange()"""
+        return self.ctx.srs_basis(self.handle)[0]
+
+    def lagrange(self, group_order, tables=True):
+        """the Setup over [L_i(tau)] G for the group_order-th roots of unity (a power of two, at most the number of powers): same
+        context, same x_2.  Its commit / commit_device / commit_many_device take Lagrange polynomials of group_order values --
+        the same commitment as committing their i_ntt() to this Setup, with no transform in front of the MSM."""
+        if group_order < 1 or group_order & (group_order - 1):
+            raise BpError(-2, "Setup.lagrange", "group_order %d is not a power of two" % group_order)
+        return Setup(self.ctx.srs_lagrange(self.handle, group_order.bit_length() - 1), self.ctx, tables, self.x_2)
+
     def commit(self, polynomial):
-        """setup.rs:32-37: asserts the Monomial basis, then bucket_msm over the whole SRS"""
+        """setup.rs:32-37: asserts the Monomial basis, then bucket_msm over the whole SRS (a Setup made by lagrange(): asserts the
+        Lagrange basis and the length)"""
         c = self.ctx
         out = np.zeros(96, dtype=np.uint8)
         c.check(c._lib.bp_commit(c._h, self.handle, polynomial.values.ctypes.data, len(polynomial), polynomial.basis, FR_MONT,
                                  out.ctypes.data), "Setup.commit")
         return bytes(out)
+
+    def commit_device(self, polynomial):
+        return commit_device(self, polynomial)
+
+    def commit_many_device(self, polynomials):
+        return commit_many_device(self, polynomials)
 
 
 CIRCUIT_COLUMNS = ("ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3")

@@ -239,9 +239,15 @@ int bp_grand_product_device(bp_ctx* ctx, const void* a, const void* b, const voi
   BP_HIP(ctx, stream_wait(ctx->stream));
   return BP_OK;
 }
+// the commit rule of the SRS `srs_handle` names (rule_commit_srs); a handle the context does not know is the MSM's to refuse
+static PolyRule commit_rule(bp_ctx* ctx, uint64_t srs_handle, int basis, size_t n) {
+  const auto it = ctx->srs.find(srs_handle);
+  if (it == ctx->srs.end()) return rule_commit(basis);
+  return rule_commit_srs(basis, n, it->second.basis, it->second.n_global);
+}
 int bp_commit_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_coeffs, size_t n, int basis, uint8_t out96[96]) {
   if (!ctx || !basis_ok(basis) || !out96) return BP_ERR_INVALID_ARG;
-  BP_RULE(ctx, rule_commit(basis));
+  BP_RULE(ctx, commit_rule(ctx, srs_handle, basis, n));
   uint8_t part[144];
   BP_TRY(bp_msm_g1_partial(ctx, srs_handle, 0, d_coeffs, n, BP_FR_MONT, 1, part));
   return bp_g1_partial_to_bytes96(part, out96);
@@ -253,7 +259,8 @@ int bp_commit_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_coeffs, siz
 int bp_commit_many_device(bp_ctx* ctx, uint64_t srs_handle, const void* const* d_coeffs, const size_t* n, size_t count, int basis,
                           uint8_t* out96) {
   if (!ctx || !basis_ok(basis) || (count && (!d_coeffs || !n || !out96))) return BP_ERR_INVALID_ARG;
-  BP_RULE(ctx, rule_commit(basis));
+  BP_RULE(ctx, commit_rule(ctx, srs_handle, basis, count ? n[0] : 0));
+  for (size_t i = 1; i < count; i++) BP_RULE(ctx, commit_rule(ctx, srs_handle, basis, n[i]));
   if (count > 64) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "more than 64 commitments in one call");
   for (size_t i = 0; i < count; i++)
     if (n[i] && !d_coeffs[i]) return BP_ERR_INVALID_ARG;
@@ -290,7 +297,7 @@ int bp_grand_product(bp_ctx* ctx, const void* a, const void* b, const void* c, c
 
 int bp_commit(bp_ctx* ctx, uint64_t srs_handle, const void* coeffs, size_t n, int basis, int scalar_fmt, uint8_t out96[96]) {
   if (!ctx || !basis_ok(basis)) return BP_ERR_INVALID_ARG;
-  BP_RULE(ctx, rule_commit(basis));
+  BP_RULE(ctx, commit_rule(ctx, srs_handle, basis, n));
   return bp_msm_g1(ctx, srs_handle, coeffs, n, scalar_fmt, out96);
 }
 

@@ -10,6 +10,7 @@
 
 #include "ctx.hpp"
 #include "g1_check.hpp"
+#include "g1_ntt.hpp"
 
 #include "capi_common.hpp"
 
@@ -176,6 +177,96 @@ int bp_srs_generate(bp_ctx* ctx, size_t powers, const uint8_t tau32[32], uint64_
 }
 int bp_srs_generate_progression(bp_ctx* ctx, size_t n, const uint8_t a32[32], const uint8_t d32[32], uint64_t* srs_handle) {
   return srs_generate_common(ctx, n, a32, d32, 1, srs_handle);
+}
+
+// The Lagrange-basis SRS over the 2^log_n-th roots of unity: L = i_ntt_381 over G1 of the first 2^log_n points (g1_ntt.hpp).  The
+// transform runs on the context's own device (the leader's, for a group: the source's shards are collected there first, GPU to GPU as
+// every group path moves data) and the result is dealt out in srs_make's point ranges, each shard registered like any other SRS.
+int bp_srs_lagrange(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n, uint64_t* lagrange_handle) {
+  if (!ctx || !lagrange_handle) return BP_ERR_INVALID_ARG;
+  SrsEntry* lead;
+  BP_TRY(srs_find(ctx, srs_handle, &lead));
+  if (log_n > G1_NTT_MAX_LOG) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "log_n > 24");
+  if (lead->basis != BP_BASIS_MONOMIAL) return BP_FAIL(ctx, BP_ERR_BASIS, "the source is itself a Lagrange SRS");
+  const size_t n = (size_t)1 << log_n;
+  if (n > lead->n_global) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "2^log_n exceeds the SRS's length");
+  std::vector<SrsShard> sh;
+  BP_TRY(srs_shards(ctx, srs_handle, &sh, 0, n));
+  DeviceGuard guard(ctx->device);
+  const g1_affine* d_src = sh[0].e->d_points;            // a plain context: the resident points as they are
+  if (sh.size() > 1) {
+    g1_affine* d_in;
+    BP_TRY(ws_get(ctx, "srs.g1_ntt_in", n * sizeof(g1_affine), (void**)&d_in));
+    for (const SrsShard& s : sh) {
+      if (s.lo >= s.hi) continue;
+      const g1_affine* part = s.e->d_points + (s.lo - s.e->first);
+      const size_t bytes = (s.hi - s.lo) * sizeof(g1_affine);
+      if (!peer_path(s.m, ctx->device)) BP_HIP(ctx, hipMemcpyAsync(d_in + s.lo, part, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+      else BP_HIP(ctx, hipMemcpyPeerAsync(d_in + s.lo, ctx->device, part, s.m->device, bytes, ctx->stream));
+    }
+    d_src = d_in;
+  }
+  g1_affine* d_full = nullptr;
+  BP_HIP(ctx, hipMalloc((void**)&d_full, n * sizeof(g1_affine)));
+  int rc = g1_ntt_run(ctx, d_src, log_n, d_full);         // waits for the stream: d_full is complete behind it
+  if (rc != BP_OK) {
+    (void)hipFree(d_full);
+    return rc;
+  }
+  std::vector<uint64_t> hs;
+  for (size_t r = 0; r < sh.size() && rc == BP_OK; r++) {
+    bp_ctx* m = sh[r].m;
+    size_t lo, hi;
+    shard_range(n, r, sh.size(), &lo, &hi);
+    uint64_t h = 0;
+    if (sh.size() == 1) {
+      rc = srs_register(ctx, d_full, n, 0, n, &h);        // takes d_full over
+      d_full = nullptr;
+    } else {
+      DeviceGuard member(m->device);
+      g1_affine* d_pts = nullptr;
+      hipError_t he = hipMalloc((void**)&d_pts, std::max<size_t>(hi - lo, 1) * sizeof(g1_affine));
+      if (he == hipSuccess && hi > lo)
+        he = !peer_path(m, ctx->device) ? hipMemcpyAsync(d_pts, d_full + lo, (hi - lo) * sizeof(g1_affine), hipMemcpyDeviceToDevice, m->stream)
+                                         : hipMemcpyPeerAsync(d_pts, m->device, d_full + lo, ctx->device, (hi - lo) * sizeof(g1_affine), m->stream);
+      if (he != hipSuccess) {
+        if (d_pts) (void)hipFree(d_pts);
+        rc = fail(ctx, BP_ERR_HIP, "Lagrange SRS: shard to its member", he, __FILE__, __LINE__);
+      } else {
+        rc = lift(ctx, m, srs_register(m, d_pts, hi - lo, lo, n, &h));      // waits for m's stream: the copy is done behind it
+      }
+    }
+    if (rc == BP_OK) {
+      SrsEntry& e = m->srs[h];
+      e.basis = BP_BASIS_LAGRANGE;
+      e.log_n = log_n;
+      hs.push_back(h);
+    }
+  }
+  if (d_full) (void)hipFree(d_full);
+  if (rc != BP_OK) {
+    for (size_t k = 0; k < hs.size(); k++) (void)srs_free_one(sh[k].m, hs[k]);
+    return rc;
+  }
+  if (sh.size() > 1) ctx->srs[hs[0]].member_handle = hs;
+  *lagrange_handle = hs[0];
+  return BP_OK;
+}
+int bp_srs_basis(bp_ctx* ctx, uint64_t srs_handle, int* basis, uint32_t* log_n) {
+  if (!ctx) return BP_ERR_INVALID_ARG;
+  SrsEntry* e;
+  BP_TRY(srs_find(ctx, srs_handle, &e));
+  if (basis) *basis = e->basis;
+  if (log_n) *log_n = e->log_n;
+  return BP_OK;
+}
+// INTERNAL, not part of include/bp_msm_ntt.h (tools/srs_lagrange_timing.py): the HIP-event time of each pass of the last
+// bp_srs_lagrange on this context.  Writes min(cap, passes) values; *passes = the number of passes it ran.
+extern "C" int bpx_srs_lagrange_pass_ms(bp_ctx* ctx, float* ms, uint32_t cap, uint32_t* passes) {
+  if (!ctx || !passes || (cap && !ms)) return BP_ERR_INVALID_ARG;
+  *passes = (uint32_t)ctx->g1_ntt_pass_ms.size();
+  for (uint32_t i = 0; i < cap && i < *passes; i++) ms[i] = ctx->g1_ntt_pass_ms[i];
+  return BP_OK;
 }
 
 int bp_srs_len(bp_ctx* ctx, uint64_t srs_handle, size_t* n) {

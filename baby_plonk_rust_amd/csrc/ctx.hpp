@@ -55,6 +55,10 @@ struct SrsEntry {
   size_t first = 0;                     // global index of this device's first point
   size_t n_global = 0;                  // length of the whole SRS (== n on a single-device context)
   std::vector<uint64_t> member_handle;  // leader only: handle of the shard on member r (index 0 = the leader's own entry)
+  // BP_BASIS_MONOMIAL: powers of tau (every load and generate); BP_BASIS_LAGRANGE: [L_i(tau)] G over the 2^log_n-th roots of unity
+  // (bp_srs_lagrange; n_global == 2^log_n).  Every shard's entry carries both.
+  int basis = BP_BASIS_MONOMIAL;
+  uint32_t log_n = 0;
 };
 
 // preprocessed circuit of the native prover (prover.hip): CommonPreprocessedInput (program.rs:34-50) resident in HBM,
@@ -190,6 +194,7 @@ struct bp_ctx {
   uint64_t comm_collectives = 0;                   // collectives this context has enqueued on its communicator(s) (bp_comm_stats)
   bool comm_init_stuck = false;                    // an ncclCommInitRank of this context ran into the bound: its helper thread is still inside RCCL
   uint64_t free_bytes_probe = 0;                   // tests only (bpx_set_free_bytes_probe): the free-memory reading bp_srs_precompute decides on; 0 = hipMemGetInfo
+  std::vector<float> g1_ntt_pass_ms;               // g1_ntt_run: HIP-event time of each pass of the last transform on this context
   bool gen_table_ready = false;                    // srs_generate_run: the generator's multiples were built into gen_table_ptr
   const void* gen_table_ptr = nullptr;
   void* pinned = nullptr;                          // small pinned staging buffer (window sums etc.)
@@ -333,6 +338,8 @@ int srs_subgroup_run(bp_ctx* ctx, const g1_affine* d_pts, size_t n, uint64_t* ba
 int srs_encode48_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes);
 int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affine* d_out);
 int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t first, size_t n, g1_affine* d_out);
+// the inverse transform over G1 of d_in[0 .. 2^log_n) (g1_ntt.hpp) -> affine points; waits for the stream
+int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_out);
 
 void comm_release(bp_ctx* ctx);                   // capi_comm.hip: destroys the context's communicator, if any
 int side_ctx_get(bp_ctx* ctx, bp_ctx** out);       // creates ctx->side and its events on first use (capi_ctx.hip)

@@ -51,6 +51,13 @@ inline PolyRule rule_div(size_t na_eff, size_t nb_eff, size_t* nq) {
 }
 inline PolyRule rule_evaluate(int basis) { return rule_monomial(basis, "coeffs_evaluate needs the Monomial basis"); }       // polynomial.rs:35
 inline PolyRule rule_commit(int basis) { return rule_monomial(basis, "commit needs the Monomial basis (setup.rs:34)"); }
+// Setup::commit against an SRS that knows its basis: the polynomial's basis must be the SRS's.  A Monomial SRS keeps rule_commit (any
+// length: zip truncation, msm.rs:29); a Lagrange SRS (bp_srs_lagrange) takes exactly the srs_len = 2^log_n values it was made for.
+inline PolyRule rule_commit_srs(int basis, size_t n, int srs_basis, size_t srs_len) {
+  if (srs_basis == BP_BASIS_MONOMIAL) return rule_commit(basis);
+  if (basis != BP_BASIS_LAGRANGE) return {BP_ERR_BASIS, "a Lagrange SRS commits to Lagrange polynomials only"};
+  return n == srs_len ? RULE_OK : PolyRule{BP_ERR_LENGTH, "a Lagrange SRS commits to polynomials of exactly its length"};
+}
 inline PolyRule rule_grand_product(size_t n) { return n > ((size_t)1 << 25) ? PolyRule{BP_ERR_TOO_LARGE, "grand product longer than 2^25"} : RULE_OK; }
 inline PolyRule rule_roots(uint64_t group_order) {          // roots_of_unity (utils.rs:45-52); 2^32 / 0 panics in root_of_unity (:39-43)
   if (group_order == 0) return {BP_ERR_INVALID_ARG, "group_order == 0"};

@@ -9,6 +9,7 @@
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "g1_check.hpp"
+#include "g1_ntt.hpp"
 
 namespace bp {
 
@@ -270,6 +271,19 @@ __global__ void __launch_bounds__(256, 2) srs_generate_fb(fr_t a, fr_t d, int mo
     }
     out[base + k] = r;
   }
+}
+
+// ---- Lagrange-basis SRS: one pass of the inverse transform over G1 (g1_ntt.hpp) ---------------------------------------------------
+// One lane per butterfly, 2^(log_n - 1) lanes; pass 0 (FIRST) reads the affine SRS, every other pass the projective buffer the pass
+// before wrote.  Four waves per workgroup, one per SIMD: the lane keeps a point, the accumulator and the temporaries of the complete
+// addition in registers through the 255 steps of its scalar multiplication.  n_inv travels as a kernel argument: the scalar of pass 0
+// is the same for the whole grid, and so is the twiddle of a wave in every pass with at least 64 groups (g1_ntt_step's lane order).
+template <bool FIRST>
+__global__ void __launch_bounds__(256) g1_ntt_pass(uint32_t log_n, uint32_t s, const g1_affine* __restrict__ in, const g1_proj* __restrict__ src,
+                                                   g1_proj* __restrict__ dst, const fr_t* __restrict__ tw, fr_t n_inv) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= ((uint64_t)1 << (log_n - 1))) return;
+  g1_ntt_pass_at<FIRST>(log_n, s, b, in, src, dst, tw, n_inv);
 }
 
 }  // namespace bp

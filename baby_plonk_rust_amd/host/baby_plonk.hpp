@@ -304,6 +304,23 @@ class Setup {
     if (n) ctx_->check(bp_srs_export_compressed48(ctx_->raw(), handle_, 0, n, out[0].data()), "srs_export_compressed48");
     return out;
   }
+  // The Setup over [L_i(tau)] G for the group_order-th roots of unity (a power of two, at most the number of powers): the inverse NTT
+  // of the powers of tau taken in G1 on the GPU, tau unknown (bp_srs_lagrange).  Its commit() takes Lagrange polynomials of exactly
+  // group_order values and returns what this Setup's commit() returns for their i_ntt().  This Setup stays as it is.
+  Setup lagrange(size_t group_order, bool tables = true) const {
+    if (group_order == 0 || (group_order & (group_order - 1))) throw Panic(BP_ERR_NOT_POW2, "lagrange: group_order is not a power of two");
+    uint32_t log_n = 0;
+    while (((size_t)1 << log_n) < group_order) log_n++;
+    uint64_t h = 0;
+    ctx_->check(bp_srs_lagrange(ctx_->raw(), handle_, log_n, &h), "lagrange");
+    if (tables) (void)bp_srs_precompute(ctx_->raw(), h, 0);
+    return Setup(h, *ctx_);
+  }
+  Basis basis() const {
+    int b = 0;
+    ctx_->check(bp_srs_basis(ctx_->raw(), handle_, &b, nullptr), "srs_basis");
+    return (Basis)b;
+  }
   // Setup::commit over ALL ranks of the context's communicator: `slice` holds the coefficients of this rank's point range; every rank
   // receives the same commitment (bp_msm_g1_allgather: one ncclAllGather of the ranks' partial-sum records under the C ABI)
   G1 commit_over_ranks(const Polynomial& slice) const {

@@ -165,6 +165,19 @@ int  bp_srs_free(bp_ctx* ctx, uint64_t srs_handle);
 int  bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits);
 /* window_bits / windows / bytes of the tables of an SRS (all 0 without tables). */
 int  bp_srs_table_info(bp_ctx* ctx, uint64_t srs_handle, uint32_t* window_bits, uint32_t* windows, uint64_t* bytes);
+/* The Lagrange-basis SRS of a powers-of-tau SRS: for n = 2^log_n <= srs_len the new SRS holds L = i_ntt_381(P_0 .. P_{n-1}) taken in
+ * G1 (utils.rs:106-129 with G1 additions and scalar multiplications in place of the Fr ones), i.e. L_i = [L_i(tau)] G for the Lagrange
+ * polynomials over the n-th roots of unity -- computed on the GPU without tau, so it works for a ceremony file.  For every v of n
+ * values, sum_i v_i L_i is the commitment of the polynomial whose evaluations are v: bp_commit* against the new handle take
+ * BP_BASIS_LAGRANGE polynomials of exactly n values (BP_ERR_LENGTH otherwise; a Monomial polynomial is BP_ERR_BASIS), with no
+ * inverse transform in front and with the column's small values visible to the MSM.  The new handle is an ordinary SRS of n points
+ * (len, export, subgroup check, tables, MSM, free; sharded like any other on a bp_init_multi context); the source is untouched and
+ * points beyond n are not read.  log_n <= 24 (BP_ERR_TOO_LARGE above); an unknown handle or 2^log_n > srs_len is
+ * BP_ERR_INVALID_ARG; a source that is itself a Lagrange SRS is BP_ERR_BASIS. */
+int  bp_srs_lagrange(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n, uint64_t* lagrange_handle);
+/* BP_BASIS_MONOMIAL and 0 for a loaded or generated SRS, BP_BASIS_LAGRANGE and its log_n for one made by bp_srs_lagrange.  Either
+ * output pointer may be null. */
+int  bp_srs_basis(bp_ctx* ctx, uint64_t srs_handle, int* basis, uint32_t* log_n);
 
 /* ---- MSM: BucketMSM::bucket_msm(points, scalars, b, c) (src/msm.rs:76-118) ----------------------- */
 /* sum_{i < min(n_scalars, srs_len - first)} s_i * P_{first+i}   (zip truncation of msm.rs:29).
@@ -372,7 +385,9 @@ int  bp_commit_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_coeffs, si
 int  bp_commit_many_device(bp_ctx* ctx, uint64_t srs_handle, const void* const* d_coeffs, const size_t* n, size_t count, int basis,
                            uint8_t* out96);
 
-/* Setup::commit (setup.rs:32-37): asserts Monomial basis, MSM of the coefficients against the SRS. */
+/* Setup::commit (setup.rs:32-37): asserts Monomial basis, MSM of the coefficients against the SRS.  The three commit entry points
+ * ask one rule: the polynomial's basis must be the SRS's (bp_srs_basis) -- Monomial for every loaded or generated SRS, as in the
+ * reference; Lagrange, with exactly srs_len values, for an SRS made by bp_srs_lagrange. */
 int  bp_commit(bp_ctx* ctx, uint64_t srs_handle, const void* coeffs, size_t n, int basis, int scalar_fmt,
                uint8_t out96[96]);
 

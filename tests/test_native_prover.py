@@ -13,6 +13,7 @@ import pytest
 import baby_plonk_rust_amd as bp
 from tests import bigint_model as M
 from tests import prover_rounds as PR
+from tests.prover_helpers import proof_challenges as _challenges, split_proof as _split
 
 Q = M.Q
 HERE = os.path.dirname(__file__)
@@ -23,27 +24,6 @@ def test_host_transcript_conformance_vector():
     """merlin's published test vector through the library's C++ transcript (no GPU): pins transcript.hpp like
     tests/test_merlin_transcript.py pins its Python twin"""
     assert bp.transcript_test_vector().hex() == MERLIN_VECTOR
-
-
-def _split(blob):
-    names = ("a_1", "b_1", "c_1", "z_1", "t_lo_1", "t_mid_1", "t_hi_1", "w_zeta_1", "w_zeta_omega_1")
-    pts = {k: M.dec48(blob[48 * i: 48 * i + 48]) for i, k in enumerate(names)}
-    ev = {k: int.from_bytes(blob[432 + 32 * i: 464 + 32 * i], "little")
-          for i, k in enumerate(("a_bar", "b_bar", "c_bar", "s1_bar", "s2_bar", "z_omega_bar"))}
-    return pts, ev
-
-
-def _challenges(blob):
-    from tests.merlin_transcript import PlonkTranscript
-    tr = PlonkTranscript()
-    pt = lambda i: blob[48 * i: 48 * i + 48]
-    ev = [int.from_bytes(blob[432 + 32 * i: 464 + 32 * i], "little") for i in range(6)]
-    beta, gamma = tr.round_1(pt(0), pt(1), pt(2))
-    alpha = tr.round_2(pt(3))
-    zeta = tr.round_3(pt(4), pt(5), pt(6))
-    nu = tr.round_4(*ev)
-    mu = tr.round_5(pt(7), pt(8))
-    return dict(beta=beta, gamma=gamma, alpha=alpha, zeta=zeta, nu=nu, mu=mu)
 
 
 @pytest.mark.gpu

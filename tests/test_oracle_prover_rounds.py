@@ -8,18 +8,10 @@ import numpy as np
 from oracle import oracle as O
 from tests import bigint_model as M
 from tests import prover_rounds as PR
+from tests.prover_helpers import oracle_srs  # noqa: F401
 from tests.test_gpu_prover_rounds import decode, g1_only_verify, run_rounds, toy_circuit
 
 Q = M.Q
-
-
-def oracle_srs(powers, tau):
-    """setup.rs:12-31: sequential cur *= tau"""
-    pts, cur, t = [], O.g1_generator(), O.fr_from_int(tau)
-    for _ in range(powers):
-        pts.append(cur)
-        cur = O.g1_mul(cur, t)
-    return np.stack(pts)
 
 
 def test_toy_circuit_proof_verifies_on_the_oracle():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Randomised differential run of bp_prove: random satisfiable circuits (random gates over a pool of shared variables,
-optional public inputs, random group order 8..128, random tau, random blinders) -- the native proof bytes must equal the
+"""Randomised differential run of bp_prove: random satisfiable circuits (tests/general_circuits.py: random gates over a pool of
+shared variables, optional public inputs; random group order 8..128, random tau, random blinders) -- the native proof bytes must equal the
 reference's call sequence (tests/prover_rounds.py) run on the CPU oracle, and the G1-only verifier must accept.
     python tools/fuzz_prover.py --seconds 200 --seed 1"""
 import argparse
@@ -14,8 +14,8 @@ import baby_plonk_rust_amd as bp
 from oracle import oracle as O
 from tests import bigint_model as M
 from tests import prover_rounds as PR
-from tests.test_gpu_prover_rounds import decode, g1_only_verify, prove_with_blinding
-from tests.test_native_prover import _challenges, _circuit_from_rows, _split
+from tests.general_circuits import general_circuit
+from tests.prover_helpers import decode, g1_only_verify, proof_challenges, prove_with_blinding, split_proof
 
 Q = M.Q
 ap = argparse.ArgumentParser()
@@ -33,34 +33,7 @@ while time.time() < t_end:
     n_pub = rnd.choice([0, 0, 1, 2])
     n_gates = rnd.randrange(1, n - n_pub + 1)
     small = rnd.random() < 0.4
-    val = lambda: rnd.randrange(1 << 8) if small else rnd.randrange(Q)
-    values, names = {}, []
-
-    def new_var(v):
-        name = "v%d" % len(values)
-        values[name] = v % Q
-        names.append(name)
-        return name
-
-    wires, sel = [], dict(ql=[], qr=[], qm=[], qo=[], qc=[])
-    publics = []
-    for _ in range(n_pub):                        # "x public": row (x, -, -), ql = 1, PI = -x
-        x = new_var(val())
-        publics.append(values[x])
-        wires.append((x, None, None))
-        for k, v in (("ql", 1), ("qr", 0), ("qm", 0), ("qo", 0), ("qc", 0)):
-            sel[k].append(v)
-    for _ in range(n_gates):
-        a = rnd.choice(names) if names and rnd.random() < 0.6 else new_var(val())
-        b = rnd.choice(names) if rnd.random() < 0.6 else new_var(val())
-        ql, qr, qm, qc = (rnd.choice([0, 1, Q - 1, val()]) for _ in range(4))
-        c = new_var(ql * values[a] + qr * values[b] + qm * values[a] * values[b] + qc)      # qo = -1
-        wires.append((a, b, c))
-        for k, v in (("ql", ql), ("qr", qr), ("qm", qm), ("qo", Q - 1), ("qc", qc)):
-            sel[k].append(v)
-    rows, pk = _circuit_from_rows(wires, sel, n)
-    cols = [[values[r[j]] if r[j] else 0 for r in rows] for j in range(3)]
-    public = [(-x) % Q for x in publics] + [0] * (n - n_pub)
+    cols, pk, public, publics = general_circuit(n, n_pub, n_gates, rnd.getrandbits(64), small=small)
     tau = rnd.choice([1, 2, rnd.randrange(Q)])
     blinders = [rnd.randrange(Q) for _ in range(11)]
     setup = bp.Setup.generate_srs(n + 6, tau, tables=rnd.random() < 0.7)
@@ -74,7 +47,7 @@ while time.time() < t_end:
         print("PROOF MISMATCH", case)
         sys.exit(1)
     vk = {k: decode(v) for k, v in circuit.commitments(setup).items()}
-    if not g1_only_verify(n, tau, *_split(blob), _challenges(blob), vk, publics):
+    if not g1_only_verify(n, tau, *split_proof(blob), proof_challenges(blob), vk, publics):
         print("VERIFIER REJECTS", case)
         sys.exit(1)
     circuit.free()

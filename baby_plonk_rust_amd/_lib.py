@@ -85,6 +85,9 @@ SIGNATURES = {
     "bp_make_s_polynomials": (_int, [_u32, _vp, _vp, _vp, _vp]),
     "bp_prove": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "bp_prove_last_stats": (_int, [_vp, _vp, _pp(C.c_float)]),
+    "bp_circuit_check_sigma": (_int, [_vp, _u64, _vp]),
+    "bp_circuit_check_witness": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "bp_circuit_check_last_stats": (_int, [_vp, _vp]),
     "bp_transcript_test_vector": (_int, [_vp]),
     "bp_plonk_challenges": (_int, [_vp, _sz, _int, _vp, _pp(_sz)]),
     "bp_verify_reduce": (_int, [_vp, _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _int, _vp, _pp(_sz)]),

@@ -14,6 +14,7 @@ own tests; where the reference panics (assert!/unwrap) these raise BpError/Asser
 
 Scalars travel as numpy uint64 arrays of shape [n, 4]: the reference's Montgomery limbs (Scalar::to_array,
 scalar.rs:35-40).  Points travel in the 96-byte uncompressed encoding (g1.rs:246-260)."""
+import collections
 import ctypes as C
 
 import os
@@ -944,6 +945,66 @@ class Circuit:
         self.ctx.check(self.ctx._lib.bp_circuit_commitments(self.ctx._h, setup.handle, self.handle, out.ctypes.data), "bp_circuit_commitments")
         return {k: bytes(out[96 * i: 96 * i + 96]) for i, k in enumerate(CIRCUIT_COLUMNS)}
 
+    def check_sigma(self):
+        """bp_circuit_check_sigma: is (S1, S2, S3) a permutation of the cells?  -> SigmaReport; .ok when it is"""
+        rep = (C.c_uint64 * 4)()
+        self.ctx.check(self.ctx._lib.bp_circuit_check_sigma(self.ctx._h, self.handle, rep), "bp_circuit_check_sigma")
+        return SigmaReport(rep[0], _cell(rep[1]), rep[2], _cell(rep[3]))
+
+    def _check(self, ptrs, fmt, on_device):
+        rep = (C.c_uint64 * 5)()
+        self.ctx.check(self.ctx._lib.bp_circuit_check_witness(self.ctx._h, self.handle, *ptrs, fmt, on_device, rep), "bp_circuit_check_witness")
+        return WitnessReport(rep[0], None if rep[1] == _ABSENT else rep[1], rep[2], _cell(rep[3]), _cell(rep[4]))
+
+    def check_witness(self, a, b, c, public_input=None, fmt=FR_MONT):
+        """bp_circuit_check_witness: which gate rows and which copy constraints does the witness violate?  a, b, c, public_input as
+        Prover.prove_with_blinding takes them (fmt=FR_BYTES_LE: [n, 32] uint8 canonical bytes) -> WitnessReport; .ok when none"""
+        n = self.group_order
+        if fmt == FR_MONT:
+            cols = [_fr_array(v) for v in (a, b, c)] + ([] if public_input is None else [_fr_array(public_input)])
+        else:
+            cols = [np.ascontiguousarray(v, dtype=np.uint8).reshape(-1, 32) for v in (a, b, c) + (() if public_input is None else (public_input,))]
+        if any(len(v) != n for v in cols):
+            raise BpError(-6, "check_witness", "witness columns must have group_order entries")
+        return self._check([v.ctypes.data for v in cols] + [None] * (4 - len(cols)), fmt, 0)
+
+    def check_witness_device(self, a_ptr, b_ptr, c_ptr, pi_ptr=None, fmt=FR_MONT):
+        """same with the witness columns already in HBM (Montgomery limbs), read in place"""
+        return self._check([a_ptr, b_ptr, c_ptr, pi_ptr], fmt, 1)
+
+    def check_stats(self):
+        """{decode_ms (0: the circuit's decode was cached), upload_ms, check_ms} of the last check on this context"""
+        ms = (C.c_float * 3)()
+        self.ctx.check(self.ctx._lib.bp_circuit_check_last_stats(self.ctx._h, ms), "bp_circuit_check_last_stats")
+        return {"decode_ms": ms[0], "upload_ms": ms[1], "check_ms": ms[2]}
+
+
+_ABSENT = 0xFFFFFFFFFFFFFFFF
+
+
+def _cell(v):
+    """cell number 3 * row + col of the C ABI -> (col, row); None for an absent position"""
+    return None if v == _ABSENT else (int(v) % 3, int(v) // 3)
+
+
+class SigmaReport(collections.namedtuple("SigmaReport", "bad_labels first_bad_label bad_indegree first_bad_indegree")):
+    """counts, and the lowest cell as (col, row), of S values that are no cell label and of cells that are the target of != 1 cells"""
+    __slots__ = ()
+
+    @property
+    def ok(self):
+        return self.bad_labels == 0 and self.bad_indegree == 0
+
+
+class WitnessReport(collections.namedtuple("WitnessReport", "gate_rows first_gate_row copy_cells first_copy_cell first_copy_target")):
+    """rows with a non-zero gate residual (count, lowest row) and cells whose value differs from the value at sigma(cell) (count,
+    lowest such cell and its sigma, as (col, row))"""
+    __slots__ = ()
+
+    @property
+    def ok(self):
+        return self.gate_rows == 0 and self.copy_cells == 0
+
 
 class Prover:
     """src/prover.rs:50-175 behind bp_prove: rounds 1-5 on the GPU, Fiat-Shamir transcript on the host"""
@@ -978,6 +1039,10 @@ class Prover:
         c_.check(c_._lib.bp_prove(c_._h, self.setup.handle, self.circuit.handle, a_ptr, b_ptr, c_ptr, pi_ptr, FR_MONT, 1, bl.ctypes.data,
                                   out.ctypes.data), "bp_prove")
         return bytes(out)
+
+    def check(self, a, b, c, public_input=None, fmt=FR_MONT):
+        """where would prove_with_blinding refuse this witness?  (Circuit.check_witness) -> WitnessReport"""
+        return self.circuit.check_witness(a, b, c, public_input, fmt)
 
     def last_stats(self):
         r, t = (C.c_float * 5)(), C.c_float()

@@ -89,6 +89,10 @@ struct CircuitEntry {
   fr_t* ginv_pow = nullptr;   // g^-i, i < 4n
   CosetConsts cc;             // g, w_4n, the four s_j, 1 / (X^n - 1) on the coset ...: computed once, in circuit_build (prover_host.hpp)
   std::vector<CosetShare> split;       // group contexts only: round 3 by coset over the members (empty otherwise)
+  // bp_circuit_check_sigma / _witness: S1 S2 S3 decoded to cell numbers (3 * row + col -> 3 * row' + col', sigma_decode.hpp), 3n words,
+  // made by the first check of the circuit and kept; sigma_report: what bp_circuit_check_sigma said then
+  uint32_t* sigma_target = nullptr;
+  uint64_t sigma_report[4] = {0, 0, 0, 0};
 };
 
 struct MemberWorker;     // persistent host thread of one member of a group context (capi_ctx.hip)
@@ -170,6 +174,7 @@ struct bp_ctx {
   // 2 partition; 0 the experiment build's counting sort), pb, packed, flat, wide8, fixup (0 per bucket, 1 per edge), n_wide, chunk
   uint32_t msm_path[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float prove_ms[6] = {0, 0, 0, 0, 0, 0};            // host wall clock of rounds 1..5 and of the whole bp_prove
+  float check_ms[3] = {0, 0, 0};                     // last bp_circuit_check_*: sigma decode (0: cached), upload + conversion, the check kernel
   bool msm_async_pending = false;  // bp_msm_g1_blob_device_async enqueued an MSM whose events have not been read yet
   float ntt_ms = 0;
   bool ntt_async_pending = false;  // bp_ntt_fr_device_async enqueued a transform whose events have not been read yet

@@ -128,6 +128,8 @@ void circuit_release(CircuitEntry& e) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
+  if (e.sigma_target) (void)hipFree(e.sigma_target);
+  e.sigma_target = nullptr;
   for (CosetShare& sh : e.split) {
     DeviceGuard guard(sh.member ? sh.member->device : 0);
     if (sh.member) (void)hipStreamSynchronize(sh.member->stream);

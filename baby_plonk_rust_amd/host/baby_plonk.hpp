@@ -362,6 +362,28 @@ struct Proof {
   }
 };
 
+// What bp_circuit_check_sigma / bp_circuit_check_witness report.  A cell is (column 0 1 2 = A B C, row); present == false: none.
+struct Cell {
+  bool present = false;
+  uint32_t column = 0;
+  uint64_t row = 0;
+  static Cell of(uint64_t v) { return v == UINT64_MAX ? Cell{} : Cell{true, (uint32_t)(v % 3), v / 3}; }
+};
+struct SigmaReport {
+  uint64_t bad_labels;           // values of S1 S2 S3 that are no cell label, and the lowest such cell
+  Cell first_bad_label;
+  uint64_t bad_indegree;         // cells that are the target of != 1 cells, and the lowest of them
+  Cell first_bad_indegree;
+  bool ok() const { return bad_labels == 0 && bad_indegree == 0; }
+};
+struct WitnessReport {
+  uint64_t gate_rows;            // rows whose gate equation does not hold, and the lowest (UINT64_MAX: none)
+  uint64_t first_gate_row;
+  uint64_t copy_cells;           // cells whose value differs from the value at sigma(cell); the lowest and its sigma
+  Cell first_copy_cell, first_copy_target;
+  bool ok() const { return gate_rows == 0 && copy_cells == 0; }
+};
+
 // src/prover.rs:50-175.  The circuit front-end (Program / Assembly) stays on the reference's side; what arrives here
 // is what it produces: the preprocessed columns once, and per proof the three wire columns and the public-input column.
 class Prover {
@@ -397,6 +419,24 @@ class Prover {
                                      public_input.empty() ? nullptr : public_input.data(), BP_FR_MONT, 0, bl, proof.bytes.data()),
                             "Prover::prove");
     return proof;
+  }
+
+  // bp_circuit_check_sigma: is (S1, S2, S3) a permutation of the 3 * group_order cells?
+  SigmaReport check_sigma() const {
+    uint64_t r[4];
+    setup_->context().check(bp_circuit_check_sigma(setup_->context().raw(), circuit_, r), "Prover::check_sigma");
+    return {r[0], Cell::of(r[1]), r[2], Cell::of(r[3])};
+  }
+  // bp_circuit_check_witness: where prove_with_blinding would refuse this witness (prover.rs:319, :615), by row and by cell
+  WitnessReport check_witness(const std::vector<Scalar>& a, const std::vector<Scalar>& b, const std::vector<Scalar>& c,
+                              const std::vector<Scalar>& public_input = {}) const {
+    if (a.size() != n_ || b.size() != n_ || c.size() != n_ || (!public_input.empty() && public_input.size() != n_))
+      throw Panic(BP_ERR_LENGTH, "witness columns must have group_order entries");
+    uint64_t r[5];
+    setup_->context().check(bp_circuit_check_witness(setup_->context().raw(), circuit_, a.data(), b.data(), c.data(),
+                                                     public_input.empty() ? nullptr : public_input.data(), BP_FR_MONT, 0, r),
+                            "Prover::check_witness");
+    return {r[0], r[1], r[2], Cell::of(r[3]), Cell::of(r[4])};
   }
 
  private:

@@ -425,6 +425,29 @@ int  bp_prove(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, const v
               uint8_t proof[624]);
 /* Host wall-clock milliseconds of rounds 1..5 and of the whole last bp_prove on this ctx. */
 int  bp_prove_last_stats(bp_ctx* ctx, float round_ms[5], float* total_ms);
+/* Where a witness fails its circuit.  The reference panics at prover.rs:319 (z_n != 1) and :615 (r(zeta) != 0) and bp_prove
+ * answers BP_ERR_ASSERT there, after most of a proof's work and without a position; these two calls name the row and the cell,
+ * from the eight Lagrange columns the circuit handle already holds in HBM.  Cells are numbered 3 * row + col (col 0 1 2 = A B C,
+ * the numbering of bp_make_s_polynomials' wire_ids); an absent position is UINT64_MAX.  Blocking, ordered on the context's stream;
+ * a group context (bp_init_multi) runs them on its first device.  A rejected call leaves `report` untouched.
+ * Is (S1, S2, S3) a permutation of the 3 * 2^log_n cells?  Every value is decoded back from its label (col + 1) w^row
+ * (program.rs:126-137) to the cell it names: report[0] = cells whose value is no cell label, report[1] = the lowest such cell,
+ * report[2] = cells that are the target of != 1 cells, report[3] = the lowest such cell.  All counts 0 <=> sigma is a
+ * permutation.  The decode runs on the first check of a circuit (either call) and stays with the handle until bp_circuit_free:
+ * 12 bytes per row. */
+int  bp_circuit_check_sigma(bp_ctx* ctx, uint64_t circuit_handle, uint64_t report[4]);
+/* a, b, c, public_input, scalar_fmt, witness_on_device: as bp_prove takes them (a device witness is read in place).
+ * report[0] = rows whose gate equation ql a + qr b + qm a b + qo c + PI + qc (prover.rs:370-376) is not zero, report[1] = the
+ * lowest such row; report[2] = cells u whose value differs from the value at sigma(u), the cell S names at u, report[3] = the
+ * lowest such u, report[4] = its sigma(u).  BP_OK means the check ran; the witness satisfies the circuit iff report[0] ==
+ * report[2] == 0, and bp_prove answers BP_ERR_ASSERT exactly when it does not.  Values are compared as the Montgomery limbs
+ * they are.  BP_ERR_BAD_SCALAR: a BP_FR_BYTES_LE value >= q.  BP_ERR_INVALID_ARG on a circuit whose sigma is no permutation
+ * (the copy comparison means nothing then): bp_last_error names bp_circuit_check_sigma and the lowest bad cell. */
+int  bp_circuit_check_witness(bp_ctx* ctx, uint64_t circuit_handle, const void* a, const void* b, const void* c,
+                              const void* public_input, int scalar_fmt, int witness_on_device, uint64_t report[5]);
+/* HIP-event milliseconds of the last of the two calls above on this ctx: the sigma decode (0 when the circuit already had it),
+ * upload + conversion of a host witness, the check kernel. */
+int  bp_circuit_check_last_stats(bp_ctx* ctx, float stage_ms[3]);
 /* merlin conformance vector: Transcript::new("test protocol"), append_message("some label", "some data"),
  * challenge_bytes("challenge", 32) -- lets a binding check the host transcript without a GPU. */
 int  bp_transcript_test_vector(uint8_t out32[32]);

@@ -99,6 +99,10 @@ SIGNATURES = {
     "bp_pairing_check_host": (_int, [_vp, _vp, _sz, _u32, _vp, _vp, _pp(_sz)]),
     "bp_pairing_check": (_int, [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _pp(_sz)]),
     "bp_pairing_last_stats": (_int, [_vp, _vp]),
+    "bp_kzg_open_device": (_int, [_vp, _u64, _vp, _vp, _sz, _int, _vp, _vp, _int, _vp, _vp]),
+    "bp_kzg_open": (_int, [_vp, _u64, _vp, _vp, _sz, _int, _vp, _vp, _int, _vp, _vp]),
+    "bp_kzg_verify_reduce": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _int, _u32, _vp, _pp(_sz)]),
+    "bp_kzg_last_stats": (_int, [_vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

@@ -7,6 +7,7 @@ own tests; where the reference panics (assert!/unwrap) these raise BpError/Asser
   ---------------------------------------------------------------------------------------------
   Setup::generate_srs(powers, tau)   setup.rs:12-31   Setup.generate_srs(powers, tau)
   Setup::commit(&poly)               setup.rs:32-37   Setup.commit(poly)
+  (no counterpart: KZG open / check)                  Setup.open(polys, z, nu) / Setup.verify_openings(openings)
   BucketMSM::bucket_msm(p, s, b, c)  msm.rs:76-118    BucketMSM.bucket_msm(points, scalars, b, c)
   ntt_381 / i_ntt_381                utils.rs:63,106  ntt_381(values) / i_ntt_381(values)
   root_of_unity / roots_of_unity     utils.rs:39-52   root_of_unity(n) / roots_of_unity(n)
@@ -456,6 +457,46 @@ class Context:
         ms = (C.c_float * 3)()
         self.check(self._lib.bp_pairing_last_stats(self._h, ms), "bp_pairing_last_stats")
         return dict(zip(("prepare_upload_ms", "miller_ms", "final_exp_ms"), [float(v) for v in ms]))
+
+    def kzg_verify_reduce(self, commitments, z, ys, nu, proofs, weights=None, checks=0, fmt=FR_MONT):
+        """bp_kzg_verify_reduce: m opening claims -> (A96, B96) with  batch holds  <=>  pairing(A, x_2) == pairing(B, G2 generator).
+        commitments: m x count x 96 bytes (row i = claim i); z, nu, weights: [m] scalars; ys: [m, count] scalars; proofs: m x 96
+        bytes; nu may be None with count == 1, weights with m <= 1.  Scalars as in verify_reduce.  checks=1 adds the subgroup test
+        of every point.  A rejected claim raises BpError whose `index` is the lowest failing claim."""
+        width, dt = (4, np.uint64) if fmt == FR_MONT else (32, np.uint8)
+        rec = np.frombuffer(bytes(proofs), dtype=np.uint8).copy()
+        com = np.frombuffer(bytes(commitments), dtype=np.uint8).copy()
+        if len(rec) % 96 or len(com) % 96:
+            raise BpError(-6, "kzg_verify_reduce", "points: 96-byte records expected")
+        m = len(rec) // 96
+        count = len(com) // 96 // m if m else 1
+        if m and len(com) != m * count * 96:
+            raise BpError(-6, "kzg_verify_reduce", "%d commitments do not fit %d claims" % (len(com) // 96, m))
+
+        def scalars(a, n, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != n * width:
+                raise BpError(-6, "kzg_verify_reduce", "%s: %d scalars expected" % (name, n))
+            return a
+        z, ys, nu, w = scalars(z, m, "z"), scalars(ys, m * count, "ys"), scalars(nu, m, "nu"), scalars(weights, m, "weights")
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        out, bad = np.zeros(192, dtype=np.uint8), C.c_size_t()
+        rc = self._lib.bp_kzg_verify_reduce(self._h, ptr(com), m, count, ptr(z), ptr(ys), ptr(nu), ptr(rec), ptr(w), fmt, checks, out.ctypes.data,
+                                            C.byref(bad))
+        try:
+            self.check(rc, "bp_kzg_verify_reduce")
+        except BpError as e:
+            e.index = bad.value if rc in (-3, -4) and bad.value != C.c_size_t(-1).value else None
+            raise
+        return out[:96].tobytes(), out[96:].tobytes()
+
+    def kzg_stats(self):
+        """milliseconds of the last Setup.open on this context (values and quotient; the commit) and of the last kzg_verify_reduce"""
+        ms = (C.c_float * 3)()
+        self.check(self._lib.bp_kzg_last_stats(self._h, ms), "bp_kzg_last_stats")
+        return dict(zip(("values_quotient_ms", "commit_ms", "reduce_ms"), [float(v) for v in ms]))
 
     def set_stream(self, stream_ptr):
         self.check(self._lib.bp_set_stream(self._h, stream_ptr), "bp_set_stream")
@@ -915,6 +956,63 @@ class Setup:
 
     def commit_many_device(self, polynomials):
         return commit_many_device(self, polynomials)
+
+    def open(self, polys, z, nu=None):
+        """KZG opening of one polynomial, or of a list of up to 16 (all Polynomial or all DevicePolynomial), at the point z
+        (bp_kzg_open / bp_kzg_open_device): returns (ys, W96) -- ys [count, 4] the values f_j(z), W96 the ONE proof for
+        sum_j nu^j f_j.  The polynomials must be in this Setup's basis: Monomial against the powers of tau, Lagrange (group_order
+        values, never transformed) against a Setup made by lagrange().  z, nu: Montgomery limbs; nu may be None for one polynomial."""
+        ps = [polys] if isinstance(polys, _PolynomialOps) else list(polys)
+        if not ps or any(not ps[0]._same_kind(p) or p.basis != ps[0].basis for p in ps):
+            raise BpError(-1, "Setup.open", "one kind and one basis of polynomial expected (and at least one)")
+        c, k = self.ctx, len(ps)
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(4)
+        nu = None if nu is None else np.ascontiguousarray(nu, dtype=np.uint64).reshape(4)
+        ptrs = (C.c_void_p * k)(*[p._ptr() if len(p) else None for p in ps])
+        lens = (C.c_size_t * k)(*[len(p) for p in ps])
+        ys, w = np.zeros((k, 4), dtype=np.uint64), np.zeros(96, dtype=np.uint8)
+        fn = getattr(c._lib, "bp_kzg_open" + ps[0]._SUFFIX)
+        c.check(fn(c._h, self.handle, ptrs, lens, k, ps[0].basis, z.ctypes.data, None if nu is None else nu.ctypes.data, FR_MONT,
+                   ys.ctypes.data, w.ctypes.data), "Setup.open")
+        return ys, bytes(w)
+
+    def opening_pairing_inputs(self, openings, weights=None, checks=0):
+        """the claims of a list of Opening records (one polynomial count for all) reduced to (A96, B96): they hold iff
+        pairing(A, x_2) == pairing(B, G2 generator).  weights: one scalar per claim, drawn after the claims were received, >= 128
+        bits of entropy each (None: a single claim).  checks=1 adds the subgroup test of every commitment and proof."""
+        openings = [openings] if isinstance(openings, Opening) else list(openings)
+        com = []
+        for o in openings:
+            cs = [o.commitments] if isinstance(o.commitments, (bytes, bytearray)) else list(o.commitments)
+            com.append(b"".join(bytes(x) for x in cs))
+        if len(set(len(x) for x in com)) > 1:
+            raise BpError(-6, "Setup.opening_pairing_inputs", "every claim must open the same number of polynomials")
+        m = len(openings)
+        limbs = lambda vals, n: np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.uint64).reshape(n, 4) for v in vals])) if m else np.zeros((0, 4), np.uint64)
+        count = len(com[0]) // 96 if m else 1
+        has_nu = [o.nu is not None for o in openings]
+        if m and any(has_nu) != all(has_nu):
+            raise BpError(-1, "Setup.opening_pairing_inputs", "nu: given for every claim or for none")
+        nu = limbs([o.nu for o in openings], 1) if m and all(has_nu) else None
+        return self.ctx.kzg_verify_reduce(b"".join(com), limbs([o.z for o in openings], 1), limbs([o.ys for o in openings], count), nu,
+                                          b"".join(bytes(o.proof) for o in openings), weights, checks)
+
+    def verify_openings(self, openings, weights=None, host=True):
+        """do the claims hold against this Setup's x_2?  opening_pairing_inputs, then one pairing check, on the host or on the
+        GPU.  weights=None with several claims draws 128-bit weights here (the claims are in hand by then)."""
+        if self.x_2 is None:
+            raise BpError(-1, "Setup.verify_openings", "the setup has no x_2 (pass x_2= to Setup.from_points / from_compressed)")
+        openings = [openings] if isinstance(openings, Opening) else list(openings)
+        if weights is None and len(openings) > 1:
+            import secrets
+            weights = scalars_from_ints([secrets.randbits(128) | 1 << 127 for _ in openings])
+        pair = self.opening_pairing_inputs(openings, weights)
+        return pairing_check([pair], self.x_2, ctx=self.ctx, host=host)[0]
+
+
+Opening = collections.namedtuple("Opening", "commitments z ys nu proof")
+Opening.__doc__ = """one KZG claim: `commitments` (96 bytes, or a list of them) open at `z` to the values `ys` ([count, 4]), combined by
+`nu` (None for one polynomial), with the proof `proof` (96 bytes) -- what Setup.commit and Setup.open return, put together"""
 
 
 CIRCUIT_COLUMNS = ("ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3")

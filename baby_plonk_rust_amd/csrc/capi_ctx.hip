@@ -353,6 +353,12 @@ void bp_destroy(bp_ctx* ctx) {
       (void)hipEventDestroy(e);
       e = nullptr;
     }
+  for (auto& e : ctx->kzg_ev)
+    if (e) {
+      DeviceGuard guard(ctx->device);
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
   for (auto& e : ctx->seam_ev)
     if (e) {
       DeviceGuard guard(ctx->device);

@@ -145,6 +145,12 @@ struct bp_ctx {
   // bp_pairing_check: the four boundaries of its three stages (prepare + upload + decode | Miller loops | final exponentiations)
   hipEvent_t pairing_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float pairing_ms[3] = {0, 0, 0};
+  // bp_kzg_open(_device) and bp_kzg_verify_reduce: [0..2] the boundaries of an opening's two stages (values + quotient | commit),
+  // [3..4] the two ends of a reduce; kzg_roots_*: the domain whose roots the workspace "kzg.roots" holds
+  hipEvent_t kzg_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  float kzg_ms[3] = {0, 0, 0};
+  const void* kzg_roots_ptr = nullptr;
+  uint32_t kzg_roots_log_n = 0;
   std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
   hipEvent_t seam_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // bp_msm_g1_projective144: piece k uploaded and normalised (recorded on the side stream)
   hipStream_t stream = nullptr;
@@ -345,8 +351,15 @@ int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affin
 int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t first, size_t n, g1_affine* d_out);
 // the inverse transform over G1 of d_in[0 .. 2^log_n) (g1_ntt.hpp) -> affine points; waits for the stream
 int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_out);
+// kzg.hip: the values y_j = f_j(z) (host_y, count of them) and the quotient (sum_j nu^j f_j - sum_j nu^j y_j) / (x - z) of count
+// <= 16 HBM-resident Montgomery polynomials, in the form they are held in; *d_q is a workspace of the context, *nq its length.
+// nu_pows: nu^0 .. nu^(count-1).  Lagrange: every column has 2^log_n values, the quotient too.  Monomial: nq = max_j n_j - 1 (0: no quotient).
+int kzg_open_lagrange_run(bp_ctx* ctx, const fr_t* const* d_polys, size_t count, uint32_t log_n, const fr_t& z, const fr_t* nu_pows,
+                          fr_t* host_y, fr_t** d_q);
+int kzg_open_monomial_run(bp_ctx* ctx, const fr_t* const* d_polys, const size_t* n, size_t count, const fr_t& z, const fr_t* nu_pows,
+                          fr_t* host_y, fr_t** d_q, size_t* nq);
 
-void comm_release(bp_ctx* ctx);                   // capi_comm.hip: destroys the context's communicator, if any
+void comm_release(bp_ctx* ctx);                 // capi_comm.hip: destroys the context's communicator, if any
 int side_ctx_get(bp_ctx* ctx, bp_ctx** out);       // creates ctx->side and its events on first use (capi_ctx.hip)
 int circuit_build(bp_ctx* ctx, uint32_t log_n, fr_t* d_lag, CircuitEntry* out);
 int circuit_split_build(bp_ctx* ctx, CircuitEntry& e);      // leader of a group: the members' coset shares (prover.hip)

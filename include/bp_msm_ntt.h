@@ -544,6 +544,50 @@ int  bp_pairing_check(bp_ctx* ctx, const uint8_t x2_192[192], const uint8_t* pai
  * exponentiations (all 0 after an empty call). */
 int  bp_pairing_last_stats(bp_ctx* ctx, float stage_ms[3]);
 
+/* ---- KZG openings in the basis of the SRS, and their batch check ----
+ * bp_kzg_open_device opens `count` polynomials f_0 .. f_{count-1} at ONE point z: y_out receives the count values f_j(z) (32 bytes
+ * each) and w96 the proof W = [q(tau)] G for q = (g - g(z)) / (x - z), g = sum_j nu^j f_j -- one proof for all of them.  The
+ * polynomials stay in the form they are held in: against a Lagrange SRS (bp_srs_lagrange) the values come from the barycentric
+ * formula, the quotient is a pointwise expression over one batched inversion (z on the domain included: the value is then
+ * f_{j,m} and q_m the closed form of the derivative), and the proof is one commit to the same SRS -- no transform anywhere.
+ * Against a powers-of-tau SRS the quotient is the TRUE quotient (max_j n_j - 1 coefficients; unlike bp_poly_div nothing is squeezed
+ * out).
+ *   d_polys, n     count pointers to HBM-resident Montgomery vectors on the context's primary device, and their lengths; n_j = 0 is
+ *                  the zero polynomial (its pointer is ignored).  1 <= count <= 16, else BP_ERR_INVALID_ARG.
+ *   basis          must be the basis of the SRS (bp_srs_basis), else BP_ERR_BASIS.  BP_BASIS_LAGRANGE: every n_j == srs_len, else
+ *                  BP_ERR_LENGTH.  BP_BASIS_MONOMIAL: max_j n_j - 1 <= srs_len, else BP_ERR_LENGTH (a commit would silently stop
+ *                  at the end of the SRS, and the proof would be false).
+ *   z32, nu32      the point and the combiner, in scalar_fmt; nu32 may be NULL only with count == 1 (BP_ERR_INVALID_ARG otherwise).
+ *                  y_out is written in scalar_fmt too.  A canonical-bytes scalar >= q is BP_ERR_BAD_SCALAR.
+ * An empty or zero quotient gives the identity encoding, 0x40 then zeros.  An unknown handle is BP_ERR_INVALID_ARG.  A
+ * bp_init_multi context does the field work on its primary device and the commit through its sharded SRS.  Blocking. */
+int  bp_kzg_open_device(bp_ctx* ctx, uint64_t srs_handle, const void* const* d_polys, const size_t* n, size_t count, int basis,
+                        const void* z32, const void* nu32_or_null, int scalar_fmt, void* y_out, uint8_t w96[96]);
+/* The same for polynomials in host memory, in scalar_fmt (a BP_FR_BYTES_LE value >= q is BP_ERR_BAD_SCALAR). */
+int  bp_kzg_open(bp_ctx* ctx, uint64_t srs_handle, const void* const* polys, const size_t* n, size_t count, int basis,
+                 const void* z32, const void* nu32_or_null, int scalar_fmt, void* y_out, uint8_t w96[96]);
+/* m claims "the commitments C_{i,0} .. C_{i,count-1} open at z_i to y_{i,0} .. y_{i,count-1}, combined by nu_i, with proof W_i"
+ * reduced to two G1 points: out192 = A || B in the record format of bp_pairing_check, with
+ *   A = sum_i r_i W_i
+ *   B = sum_i r_i (sum_j nu_i^j (C_ij - y_ij G) + z_i W_i)
+ * The batch holds iff pairing(A, x_2) == pairing(B, G2Affine::generator()) (up to the 2^-128 of the weights); this call does not
+ * decide it.
+ *   commitments96  m x count records, row i = claim i;  proofs96: m records;  z, nu, weights: m scalars;  y: m x count scalars, all
+ *                  in scalar_fmt (a canonical-bytes value >= q: BP_ERR_BAD_SCALAR with the lowest such claim in *first_bad).
+ *   nu_or_null     NULL only with count == 1.  1 <= count <= 16.
+ *   weights        m scalars r_i, drawn by the caller AFTER it has received the claims, 128 bits of entropy or more each.  NULL means
+ *                  r_i = 1 and is accepted for m <= 1 only (BP_ERR_INVALID_ARG otherwise).
+ *   checks         every point is always checked for canonical coordinates, flags and the curve; checks & 1 adds the subgroup test.
+ *                  A rejected point is BP_ERR_BAD_POINT with the lowest failing claim in *first_bad (may be NULL); out192 is then left
+ *                  untouched.  On success *first_bad = SIZE_MAX.
+ * m == 0: BP_OK, A = B = identity.  The scalars are computed on the host, the points decoded and summed (two MSMs over
+ * m count + m + 1 and m points) on the context's primary device.  Blocking. */
+int  bp_kzg_verify_reduce(bp_ctx* ctx, const uint8_t* commitments96, size_t m, size_t count, const void* z, const void* y,
+                          const void* nu_or_null, const uint8_t* proofs96, const void* weights_or_null, int scalar_fmt,
+                          uint32_t checks, uint8_t out192[192], size_t* first_bad);
+/* Milliseconds of the last opening's two stages -- values and quotient; the commit -- and of the last bp_kzg_verify_reduce. */
+int  bp_kzg_last_stats(bp_ctx* ctx, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,18 +11,8 @@ using namespace bp;
 
 namespace {
 
-// the HIP events of one call: created on entry, destroyed on every way out
-struct CheckEvents {
-  hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~CheckEvents() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  int create(bp_ctx* ctx, int count) {
-    for (int i = 0; i < count; i++) BP_HIP(ctx, hipEventCreate(&e[i]));
-    return BP_OK;
-  }
-};
+// the context's six "check" events: [0..1] around the sigma decode, [2..3] around upload + conversion, [4..5] around the check kernel
+int check_events(bp_ctx* ctx, hipEvent_t** ev) { return ev_get(ctx, "check", 6, hipEventDefault, ev); }
 
 dim3 blocks_of(size_t lanes) { return dim3((unsigned)((lanes + 255) / 256)); }
 
@@ -86,10 +76,10 @@ int bp_circuit_check_sigma(bp_ctx* ctx, uint64_t circuit_handle, uint64_t report
   auto it = ctx->circuits.find(circuit_handle);
   if (it == ctx->circuits.end()) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "unknown circuit handle");
   DeviceGuard guard(ctx->device);
-  CheckEvents ev;
-  BP_TRY(ev.create(ctx, 2));
+  hipEvent_t* ev;
+  BP_TRY(check_events(ctx, &ev));
   float decode_ms = 0;
-  BP_TRY(sigma_ensure(ctx, it->second, ev.e[0], ev.e[1], &decode_ms));
+  BP_TRY(sigma_ensure(ctx, it->second, ev[0], ev[1], &decode_ms));
   const float ms[3] = {decode_ms, 0, 0};
   memcpy(ctx->check_ms, ms, sizeof ms);
   memcpy(report, it->second.sigma_report, 4 * sizeof(uint64_t));
@@ -105,10 +95,10 @@ int bp_circuit_check_witness(bp_ctx* ctx, uint64_t circuit_handle, const void* a
   CircuitEntry& cir = it->second;
   const size_t n = (size_t)1 << cir.log_n;
   DeviceGuard guard(ctx->device);
-  CheckEvents ev;
-  BP_TRY(ev.create(ctx, 6));
+  hipEvent_t* ev;
+  BP_TRY(check_events(ctx, &ev));
   float ms[3] = {0, 0, 0};
-  BP_TRY(sigma_ensure(ctx, cir, ev.e[0], ev.e[1], &ms[0]));
+  BP_TRY(sigma_ensure(ctx, cir, ev[0], ev[1], &ms[0]));
   if (cir.sigma_report[0] || cir.sigma_report[2]) {
     const uint64_t cell = cir.sigma_report[0] ? cir.sigma_report[1] : cir.sigma_report[3];
     char msg[200];
@@ -121,7 +111,7 @@ int bp_circuit_check_witness(bp_ctx* ctx, uint64_t circuit_handle, const void* a
   const void* src[4] = {a, b, c, public_input};
   const fr_t* col[4] = {(const fr_t*)a, (const fr_t*)b, (const fr_t*)c, (const fr_t*)public_input};
   uint32_t* d_bad = nullptr;
-  BP_HIP(ctx, hipEventRecord(ev.e[2], ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
   if (!witness_on_device) {
     fr_t* wit;
     BP_TRY(ws_get(ctx, "check.witness", 4 * n * sizeof(fr_t), (void**)&wit));
@@ -133,21 +123,21 @@ int bp_circuit_check_witness(bp_ctx* ctx, uint64_t circuit_handle, const void* a
     BP_TRY(fr_bad_word(ctx, scalar_fmt, &d_bad));
     if (scalar_fmt == BP_FR_BYTES_LE) BP_TRY(fr_convert_run(ctx, wit, count * n, 0, d_bad));
   }
-  BP_HIP(ctx, hipEventRecord(ev.e[3], ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
   unsigned long long* status;
   BP_TRY(status_begin(ctx, &status));
-  BP_HIP(ctx, hipEventRecord(ev.e[4], ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
   hipLaunchKernelGGL(witness_check, blocks_of(n), dim3(256), 0, ctx->stream, col[0], col[1], col[2], col[3], cir.lag, n, cir.sigma_target, status);
   BP_HIP(ctx, hipGetLastError());
-  BP_HIP(ctx, hipEventRecord(ev.e[5], ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev[5], ctx->stream));
   unsigned long long h[4] = {0, 0, ~0ull, ~0ull};
   uint32_t bad = 0;
   BP_HIP(ctx, hipMemcpyAsync(h, status, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   if (d_bad) BP_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
   BP_HIP(ctx, stream_wait(ctx->stream));
   if (bad) return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, "witness element >= q");
-  BP_HIP(ctx, hipEventElapsedTime(&ms[1], ev.e[2], ev.e[3]));
-  BP_HIP(ctx, hipEventElapsedTime(&ms[2], ev.e[4], ev.e[5]));
+  BP_HIP(ctx, hipEventElapsedTime(&ms[1], ev[2], ev[3]));
+  BP_HIP(ctx, hipEventElapsedTime(&ms[2], ev[4], ev[5]));
   memcpy(ctx->check_ms, ms, sizeof ms);
   report[0] = h[0];
   report[1] = h[2];

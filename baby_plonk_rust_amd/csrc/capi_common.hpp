@@ -8,6 +8,30 @@
 
 inline bool fmt_ok(int fmt) { return fmt == BP_FR_BYTES_LE || fmt == BP_FR_MONT; }
 inline bool basis_ok(int b) { return b == BP_BASIS_LAGRANGE || b == BP_BASIS_MONOMIAL; }
+// why a G1 point was rejected: `reason` of a decoder's status word (g1_check.hpp), for a 48-byte compressed record or a 96-byte one
+inline const char* g1_reject_text(uint32_t reason, bool compressed) {
+  if (reason == bp::G1_BAD_ENCODING) return compressed ? "bad encoding (flag bits, or x >= p)" : "bad encoding (flag bits, or a coordinate >= p)";
+  if (reason == bp::G1_NOT_ON_CURVE) return compressed ? "not on the curve (x^3 + 4 has no square root)" : "not on the curve";
+  return "not in the prime-order subgroup";
+}
+// one 96-byte record checked on the host: canonical, flags, on the curve (the checks of bp_srs_load); false = refused.  The identity
+// (only a record with the infinity flag) passes as (0, 0).
+inline bool host_point96(bp::g1_affine& out, const uint8_t in96[96]) {
+  bp::g1_proj p;
+  if (!bp::host_decode96(p, in96)) return false;
+  if (bp::g1_is_identity(p)) {
+    out.x = out.y = bp::Fp::zero();
+    return true;
+  }
+  out.x = p.x;
+  out.y = p.y;
+  return bp::g1_affine_on_curve(out);
+}
+// (A, B) = (identity, identity): what a reduce of nothing returns
+inline void encode_identity_pair(uint8_t out192[192]) {
+  memset(out192, 0, 192);
+  out192[0] = out192[96] = 0x40;
+}
 // capi_ctx.hip
 // d_bad (bp::fr_bad_word): upload_fr raises it for a canonical-bytes input >= q; download_fr reads it with the copy that ends the
 // call and returns BP_ERR_BAD_SCALAR when it is set (`host` is then unspecified)

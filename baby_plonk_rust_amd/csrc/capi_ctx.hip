@@ -67,6 +67,17 @@ int ws_get(bp_ctx* ctx, const char* name, size_t bytes, void** out) {
   return BP_OK;
 }
 
+int ev_get(bp_ctx* ctx, const char* name, size_t count, unsigned flags, hipEvent_t** out) {
+  std::vector<hipEvent_t>& ev = ctx->events[name];
+  while (ev.size() < count) {
+    hipEvent_t e;
+    BP_HIP(ctx, hipEventCreateWithFlags(&e, flags));
+    ev.push_back(e);
+  }
+  *out = ev.data();
+  return BP_OK;
+}
+
 int pinned_get(bp_ctx* ctx, size_t bytes, void** out) {
   if (ctx->pinned_cap < bytes) {
     if (ctx->pinned) BP_HIP(ctx, hipHostFree(ctx->pinned));
@@ -247,9 +258,6 @@ int side_ctx_get(bp_ctx* ctx, bp_ctx** out) {
     int rc = ctx_create(&sd, ctx->device);
     if (rc != BP_OK) return BP_FAIL(ctx, rc, "side context");
     ctx->side = sd;
-    DeviceGuard guard(ctx->device);
-    for (auto& e : ctx->side_ev)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(ctx, BP_ERR_HIP, "side events", hipGetLastError(), __FILE__, __LINE__);
   }
   *out = ctx->side;
   return BP_OK;
@@ -329,44 +337,10 @@ void bp_destroy(bp_ctx* ctx) {
     bp_destroy(ctx->side);
     ctx->side = nullptr;
   }
-  for (auto& e : ctx->side_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  for (auto& e : ctx->verify_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  for (auto& e : ctx->verify_seg_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  for (auto& e : ctx->pairing_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  for (auto& e : ctx->kzg_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  for (auto& e : ctx->seam_ev)
-    if (e) {
-      DeviceGuard guard(ctx->device);
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
   DeviceGuard guard(ctx->device);
   if (ctx->stream) (void)stream_wait(ctx->stream);
+  for (auto& kv : ctx->events)
+    for (hipEvent_t e : kv.second) (void)hipEventDestroy(e);
   comm_release(ctx);
   if (ctx->comm_host) (void)hipHostFree(ctx->comm_host);
   for (auto& kv : ctx->ws)

@@ -17,19 +17,16 @@ using namespace bp;
 
 constexpr size_t KZG_MAX_COUNT = 16;
 
-static int kzg_events(bp_ctx* ctx) {
-  for (auto& e : ctx->kzg_ev)
-    if (!e) BP_HIP(ctx, hipEventCreate(&e));
-  return BP_OK;
-}
+// the context's five "kzg" events: [0..2] the boundaries of an opening's two stages (values + quotient | commit), [3..4] the two ends of a reduce
+static int kzg_events(bp_ctx* ctx, hipEvent_t** ev) { return ev_get(ctx, "kzg", 5, hipEventDefault, ev); }
 
 // the part both entry points share: d_polys are HBM-resident Montgomery vectors on the context's primary device
 static int kzg_open_core(bp_ctx* ctx, SrsEntry* e, uint64_t srs, const fr_t* const* d_polys, const size_t* n, size_t count, int basis, const fr_t& z,
                          const fr_t* nu, fr_t* y, g1_proj* W) {
   fr_t pows[KZG_MAX_COUNT];
   kzg_powers(nu, count, pows);
-  BP_TRY(kzg_events(ctx));
-  hipEvent_t* ev = ctx->kzg_ev;
+  hipEvent_t* ev;
+  BP_TRY(kzg_events(ctx, &ev));
   BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
   fr_t* d_q = nullptr;
   size_t nq = 0;
@@ -131,17 +128,6 @@ int bp_kzg_open(bp_ctx* ctx, uint64_t srs_handle, const void* const* polys, cons
 }
 
 // ------------------------------------------------------------------------------------------------------- the batch check
-// one record: canonical, flags, on the curve (the checks of bp_srs_load); the identity passes
-static bool kzg_point_ok(const uint8_t in96[96]) {
-  g1_proj p;
-  if (!host_decode96(p, in96)) return false;
-  if (g1_is_identity(p)) return true;
-  g1_affine a;
-  a.x = p.x;
-  a.y = p.y;
-  return g1_affine_on_curve(a);
-}
-
 static int kzg_reduce_run(bp_ctx* ctx, const uint8_t* commitments96, size_t m, size_t count, const fr_t* sc_c, const fr_t* sc_w, const fr_t* sc_a,
                           const fr_t& sc_g, const uint8_t* proofs96, uint32_t checks, uint8_t out192[192], size_t* first_bad) {
   const size_t n_c = m * count, n_pts = n_c + m, n_all = n_pts + 1;          // C_ij row by row | W_i | G
@@ -153,9 +139,10 @@ static int kzg_reduce_run(bp_ctx* ctx, const uint8_t* commitments96, size_t m, s
   BP_TRY(ws_get(ctx, "kzg.v_points", n_all * sizeof(g1_affine), (void**)&d_pts));
   BP_TRY(ws_get(ctx, "kzg.v_p28", n_all * sizeof(g1_affine28), (void**)&d_p28));
   BP_TRY(ws_get(ctx, "kzg.v_scalars", (n_all + m) * sizeof(fr_t), (void**)&d_sc));
-  BP_TRY(kzg_events(ctx));
+  hipEvent_t* ev;
+  BP_TRY(kzg_events(ctx, &ev));
   hipStream_t st = ctx->stream;
-  BP_HIP(ctx, hipEventRecord(ctx->kzg_ev[3], st));
+  BP_HIP(ctx, hipEventRecord(ev[3], st));
   const g1_affine gen = g1_affine_generator();
   BP_HIP(ctx, hipMemcpyAsync(d_bytes, commitments96, n_c * 96, hipMemcpyHostToDevice, st));
   BP_HIP(ctx, hipMemcpyAsync(d_bytes + n_c * 96, proofs96, m * 96, hipMemcpyHostToDevice, st));
@@ -166,9 +153,10 @@ static int kzg_reduce_run(bp_ctx* ctx, const uint8_t* commitments96, size_t m, s
   BP_HIP(ctx, hipMemcpyAsync(d_sc + n_all, sc_a, m * sizeof(fr_t), hipMemcpyHostToDevice, st));
   if (srs_decode_run(ctx, d_bytes, n_pts, d_pts) != BP_OK) {
     // the decoder says that a record was refused, not which: the rare path looks on the host, claim by claim
+    g1_affine pt;
     for (size_t i = 0; i < m; i++) {
-      bool ok = kzg_point_ok(proofs96 + 96 * i);
-      for (size_t j = 0; j < count && ok; j++) ok = kzg_point_ok(commitments96 + 96 * (i * count + j));
+      bool ok = host_point96(pt, proofs96 + 96 * i);
+      for (size_t j = 0; j < count && ok; j++) ok = host_point96(pt, commitments96 + 96 * (i * count + j));
       if (ok) continue;
       if (first_bad) *first_bad = i;
       char msg[120];
@@ -195,9 +183,9 @@ static int kzg_reduce_run(bp_ctx* ctx, const uint8_t* commitments96, size_t m, s
   g1_proj A, B;
   BP_TRY(msm_run(ctx, d_p28, n_all, d_sc, BP_FR_MONT, 0, 0, &B));
   BP_TRY(msm_run(ctx, d_p28 + n_c, m, d_sc + n_all, BP_FR_MONT, 0, 0, &A));
-  BP_HIP(ctx, hipEventRecord(ctx->kzg_ev[4], st));
+  BP_HIP(ctx, hipEventRecord(ev[4], st));
   BP_HIP(ctx, stream_wait(st));
-  BP_HIP(ctx, hipEventElapsedTime(&ctx->kzg_ms[2], ctx->kzg_ev[3], ctx->kzg_ev[4]));
+  BP_HIP(ctx, hipEventElapsedTime(&ctx->kzg_ms[2], ev[3], ev[4]));
   host_encode96(out192, A);
   host_encode96(out192 + 96, B);
   return BP_OK;
@@ -214,8 +202,7 @@ int bp_kzg_verify_reduce(bp_ctx* ctx, const uint8_t* commitments96, size_t m, si
   if (first_bad) *first_bad = SIZE_MAX;
   ctx->kzg_ms[2] = 0;
   if (m == 0) {
-    memset(out192, 0, 192);
-    out192[0] = out192[96] = 0x40;
+    encode_identity_pair(out192);
     return BP_OK;
   }
   // the scalars, on the host: m (count + 2) products

@@ -383,8 +383,8 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
   DeviceGuard guard(ctx->device);
   bp_ctx* side;
   BP_TRY(side_ctx_get(ctx, &side));
-  for (auto& e : ctx->seam_ev)
-    if (!e) BP_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipEvent_t* seam_ev;                                     // [k]: piece k uploaded and normalised (recorded on the side stream)
+  BP_TRY(ev_get(ctx, "seam", SEAM_PIECES, hipEventDisableTiming, &seam_ev));
   int pieces = 2;
   {
     const char* v = knob("BP_SEAM_PIECES");
@@ -417,8 +417,8 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
       ctx->last_error = side->last_error;
       break;
     }
-    he = hipEventRecord(ctx->seam_ev[k], side->stream);
-    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->seam_ev[k], 0);
+    he = hipEventRecord(seam_ev[k], side->stream);
+    if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, seam_ev[k], 0);
     if (he != hipSuccess) {
       rc = fail(ctx, BP_ERR_HIP, "bucket_msm piece order", he, __FILE__, __LINE__);
       break;

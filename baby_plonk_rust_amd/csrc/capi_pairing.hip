@@ -35,13 +35,6 @@ int bp_pairing_check_host(const uint8_t x2_192[192], const uint8_t* pairs192, si
 // 256 CUs with two waves each; a longer call reuses the workspace pass after pass
 constexpr size_t PAIRING_PASS_LANES = (size_t)1 << 15;
 
-// The copies below read pageable host memory of this call (the lines, the caller's pairs): whatever way the function is left, the
-// stream is idle before those buffers go away.
-struct StreamDrain {
-  hipStream_t st;
-  ~StreamDrain() { (void)stream_wait(st); }
-};
-
 static int pairing_check_run(bp_ctx* ctx, const g2_affine& x2, const uint8_t* pairs192, size_t n, uint32_t checks, uint8_t* verdicts,
                              uint8_t* gt576_or_null, size_t* first_bad) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -62,12 +55,11 @@ static int pairing_check_run(bp_ctx* ctx, const g2_affine& x2, const uint8_t* pa
   BP_TRY(ws_get(ctx, "pairing.ws", pairing_ws_dwords(stride) * sizeof(uint32_t), (void**)&d_ws));
   BP_TRY(ws_get(ctx, "pairing.verdicts", n, (void**)&d_verdicts));
   if (gt576_or_null) BP_TRY(ws_get(ctx, "pairing.gt", n * GT_BYTES, (void**)&d_gt));
-  for (auto& e : ctx->pairing_ev)
-    if (!e) BP_HIP(ctx, hipEventCreate(&e));
+  hipEvent_t* ev;                                                   // the four boundaries of the three stages
+  BP_TRY(ev_get(ctx, "pairing", 4, hipEventDefault, &ev));
   hipStream_t st = ctx->stream;
-  hipEvent_t* ev = ctx->pairing_ev;
   const float prepare_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();      // the lines: host work
-  const StreamDrain drain{st};
+  const StreamDrain drain{st};                                      // the copies below read the lines and the caller's pairs: pageable memory of this call
   auto blocks = [](size_t lanes) { return dim3((unsigned)((lanes + 63) / 64)); };
 
   // stage 0: upload, decode and check the 2 n points; the call waits here and reads the status word
@@ -84,13 +76,9 @@ static int pairing_check_run(bp_ctx* ctx, const g2_affine& x2, const uint8_t* pa
   BP_HIP(ctx, hipEventElapsedTime(&ctx->pairing_ms[0], ev[0], ev[1]));
   ctx->pairing_ms[0] += prepare_ms;
   if (bad != ~0ull) {
-    const uint32_t reason = (uint32_t)(bad & 3);
     *first_bad = (size_t)(bad >> 2);
     char msg[160];
-    snprintf(msg, sizeof msg, "pair %llu: a point rejected: %s", (unsigned long long)(bad >> 2),
-             reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or a coordinate >= p)"
-             : reason == G1_NOT_ON_CURVE ? "not on the curve"
-                                         : "not in the prime-order subgroup");
+    snprintf(msg, sizeof msg, "pair %llu: a point rejected: %s", (unsigned long long)(bad >> 2), g1_reject_text((uint32_t)(bad & 3), false));
     return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
   }
 

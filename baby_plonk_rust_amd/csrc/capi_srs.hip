@@ -83,10 +83,7 @@ static size_t srs_record_bytes(int kind) { return kind == 0 ? 96 : kind == 1 ? 1
 static int srs_bad_point(bp_ctx* ctx, uint64_t index, uint32_t reason, size_t* first_bad) {
   if (first_bad) *first_bad = (size_t)index;
   char msg[160];
-  snprintf(msg, sizeof msg, "point %llu rejected: %s", (unsigned long long)index,
-           reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
-           : reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
-                                       : "not in the prime-order subgroup");
+  snprintf(msg, sizeof msg, "point %llu rejected: %s", (unsigned long long)index, g1_reject_text(reason, true));
   return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
 }
 

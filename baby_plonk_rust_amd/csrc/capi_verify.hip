@@ -42,32 +42,9 @@ int bp_plonk_challenges(const uint8_t* proofs624, size_t m, int scalar_fmt, void
   return BP_OK;
 }
 
-// one vk commitment: canonical, flags, on the curve (the checks of bp_srs_load); the identity is (0, 0)
-static bool vk_point_decode(g1_affine& out, const uint8_t in96[96]) {
-  g1_proj p;
-  if (!host_decode96(p, in96)) return false;
-  if (g1_is_identity(p)) {                                   // only a record with the infinity flag
-    out.x = out.y = Fp::zero();
-    return true;
-  }
-  out.x = p.x;
-  out.y = p.y;
-  return g1_affine_on_curve(out);
-}
-
-static void encode_identity_pair(uint8_t out192[192]) {
-  memset(out192, 0, 192);
-  out192[0] = out192[96] = 0x40;
-}
-
-static int verify_events(bp_ctx* ctx) {
-  for (auto& e : ctx->verify_ev)
-    if (!e) BP_HIP(ctx, hipEventCreate(&e));
-  return BP_OK;
-}
-
 // what stages 0-3 leave on the device for stage 4, whichever it is
 struct VerifyStaged {
+  hipEvent_t* ev = nullptr;                // the context's six "verify" events: the boundaries of the five stages, [0..4] recorded
   size_t m = 0, n_pts = 0, n_all = 0;      // proofs, 9 m proof points, 9 m + 9 points with the shared bases behind them
   fr_t *d_b = nullptr, *d_a = nullptr;     // verify_scalars' scal_b (9 m, and nine free slots behind) and scal_a (2 m)
   fr_t* d_sh = nullptr;                    // its per-proof shares of the nine shared-base scalars (9 m)
@@ -82,7 +59,7 @@ static int verify_stages_0_3(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   // the nine shared bases: eight vk commitments in the order bp_circuit_commitments writes them, then G
   g1_affine* shared_pts = staged->shared_pts;
   for (int k = 0; k < 8; k++)
-    if (!vk_point_decode(shared_pts[k], vk768 + 96 * k)) {
+    if (!host_point96(shared_pts[k], vk768 + 96 * k)) {
       char msg[96];
       snprintf(msg, sizeof msg, "verifier key: commitment %d rejected (encoding, flags or not on the curve)", k);
       return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
@@ -111,9 +88,9 @@ static int verify_stages_0_3(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   BP_TRY(ws_get(ctx, "verify.shared", n_pts * sizeof(fr_t), (void**)&d_sh));
   BP_TRY(ws_get(ctx, "verify.points", n_all * sizeof(g1_affine), (void**)&d_pts));
   BP_TRY(ws_get(ctx, "verify.status", 8, (void**)&d_status));
-  BP_TRY(verify_events(ctx));
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "verify", 6, hipEventDefault, &ev));
   hipStream_t st = ctx->stream;
-  hipEvent_t* ev = ctx->verify_ev;
 
   // stage 0: upload (pageable host memory: the copies are staged by the runtime before they return)
   BP_HIP(ctx, hipEventRecord(ev[0], st));
@@ -165,9 +142,7 @@ static int verify_stages_0_3(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
     if (pt_proof != SIZE_MAX && pt_proof <= sc_proof) {            // on a tie the point is reported
       if (first_bad) *first_bad = pt_proof;
       snprintf(msg, sizeof msg, "proof %llu: point %s rejected: %s", (unsigned long long)pt_proof, VERIFY_POINT_NAME[pt_field],
-               pt_reason == G1_BAD_ENCODING ? "bad encoding (flag bits, or x >= p)"
-               : pt_reason == G1_NOT_ON_CURVE ? "not on the curve (x^3 + 4 has no square root)"
-                                              : "not in the prime-order subgroup");
+               g1_reject_text(pt_reason, true));
       return BP_FAIL(ctx, BP_ERR_BAD_POINT, msg);
     }
     const uint32_t field = (uint32_t)(scalar_bad & 15);
@@ -177,6 +152,7 @@ static int verify_stages_0_3(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
     return BP_FAIL(ctx, BP_ERR_BAD_SCALAR, msg);
   }
 
+  staged->ev = ev;
   staged->m = m;
   staged->n_pts = n_pts;
   staged->n_all = n_all;
@@ -197,7 +173,7 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
   g1_affine28* d_p28;
   BP_TRY(ws_get(ctx, "verify.p28", n_all * sizeof(g1_affine28), (void**)&d_p28));
   hipStream_t st = ctx->stream;
-  hipEvent_t* ev = ctx->verify_ev;
+  hipEvent_t* ev = V.ev;
 
   // stage 4: B over all 9 m + 9 points, A over the slice [7 m, 9 m) of the same array
   BP_TRY(srs_to28_into(ctx, d_pts, n_all, d_p28));
@@ -251,10 +227,9 @@ static int verify_segments_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[
   BP_TRY(ws_get(ctx, "verify.seg_node", 2 * m * SEG_PT_WORDS * sizeof(uint32_t), (void**)&d_node));
   BP_TRY(ws_get(ctx, "verify.seg_run", 2 * S * N28 * sizeof(uint32_t), (void**)&d_run));
   BP_TRY(ws_get(ctx, "verify.seg_out", S * 192, (void**)&d_out));
-  for (auto& e : ctx->verify_seg_ev)
-    if (!e) BP_HIP(ctx, hipEventCreate(&e));
+  hipEvent_t *ev = V.ev, *sev;                                       // sev: the two boundaries inside stage 4
+  BP_TRY(ev_get(ctx, "verify.seg", 2, hipEventDefault, &sev));
   hipStream_t st = ctx->stream;
-  hipEvent_t *ev = ctx->verify_ev, *sev = ctx->verify_seg_ev;
   auto blocks = [](size_t n, size_t per) { return dim3((unsigned)((n + per - 1) / per)); };
 
   // the shared-base terms take the split form only where the endomorphism is [x^2]: on a key inside the subgroup

@@ -133,26 +133,19 @@ struct bp_ctx {
   std::vector<bp_ctx*> lanes;
   // One more single-device context on this device for prover work that does not wait for a Fiat-Shamir challenge (the coset
   // evaluations of a, b, c and PI, prover.rs:386-450, are known after round 1): enqueued beside rounds 1-2, it fills the GPU time
-  // the commitments' latency-bound tails and the host's transcript steps leave idle.  side_ev: [0] inputs ready, [1] side work done.
+  // the commitments' latency-bound tails and the host's transcript steps leave idle.  Events "side": [0] inputs ready, [1] side work done.
   bp_ctx* side = nullptr;
-  hipEvent_t side_ev[2] = {nullptr, nullptr};
-  hipEvent_t verify_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // bp_verify_reduce: the boundaries of its five stages
   float verify_ms[5] = {0, 0, 0, 0, 0};              // upload, transcript, scalars, decode + subgroup check, MSMs of the last bp_verify_reduce
-  // bp_verify_reduce_segments: the two boundaries inside its last stage, and that stage's split (multiplications | per-proof sums,
-  // segment tree and shared bases | normalisation and encoding)
-  hipEvent_t verify_seg_ev[2] = {nullptr, nullptr};
+  // bp_verify_reduce_segments: the split of its last stage (multiplications | per-proof sums, segment tree and shared bases |
+  // normalisation and encoding)
   float verify_seg_ms[3] = {0, 0, 0};
-  // bp_pairing_check: the four boundaries of its three stages (prepare + upload + decode | Miller loops | final exponentiations)
-  hipEvent_t pairing_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float pairing_ms[3] = {0, 0, 0};
-  // bp_kzg_open(_device) and bp_kzg_verify_reduce: [0..2] the boundaries of an opening's two stages (values + quotient | commit),
-  // [3..4] the two ends of a reduce; kzg_roots_*: the domain whose roots the workspace "kzg.roots" holds
-  hipEvent_t kzg_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  float pairing_ms[3] = {0, 0, 0};                   // bp_pairing_check: prepare + upload + decode | Miller loops | final exponentiations
+  // bp_kzg_open(_device): values + quotient | commit; bp_kzg_verify_reduce: the whole reduce; kzg_roots_*: the domain whose roots
+  // the workspace "kzg.roots" holds
   float kzg_ms[3] = {0, 0, 0};
   const void* kzg_roots_ptr = nullptr;
   uint32_t kzg_roots_log_n = 0;
   std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
-  hipEvent_t seam_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // bp_msm_g1_projective144: piece k uploaded and normalised (recorded on the side stream)
   hipStream_t stream = nullptr;
   bool own_stream = true;
   // experiment (BP_ACC_LOW_PRIORITY=1): msm_accumulate runs on a lowest-priority stream of its own, chained to `stream` by
@@ -161,7 +154,8 @@ struct bp_ctx {
   hipStream_t acc_stream = nullptr;
   hipEvent_t acc_ev[2] = {nullptr, nullptr};
   std::string last_error;
-  std::map<std::string, bp::DevBuf> ws;            // grow-only named device workspaces
+  std::map<std::string, bp::DevBuf> ws;            // grow-only named device workspaces (ws_get)
+  std::map<std::string, std::vector<hipEvent_t>> events;      // grow-only named sets of HIP events (ev_get)
   std::map<uint64_t, bp::SrsEntry> srs;
   std::map<uint64_t, bp::CircuitEntry> circuits;
   uint64_t next_handle = 1;
@@ -273,9 +267,22 @@ inline bool peer_path(const bp_ctx* m, int other_device) {
 // calls of this library are a few milliseconds long and wait several times each (nine commitments and ~30 small results per
 // proof), so the wait polls hipStreamQuery for the first few milliseconds and only then blocks (experiment build: BP_WAIT_BLOCK=1 blocks at once).
 hipError_t stream_wait(hipStream_t st);
+// Copies that read pageable host memory of the call (prepared lines, the caller's records): whatever way the function is left, the
+// stream is idle before those buffers go away.
+struct StreamDrain {
+  hipStream_t st;
+  ~StreamDrain() { (void)stream_wait(st); }
+};
 
 // device workspace `name` of at least `bytes` (contents undefined after growth)
 int ws_get(bp_ctx* ctx, const char* name, size_t bytes, void** out);
+// the context's HIP events `name`, at least `count` of them, created on first use with `flags` and kept until bp_destroy; *out is
+// valid until the next ev_get of the same name (a larger count may move the set).  Every event an entry point records to time its
+// stages or to order the context's stream against the side stream comes from here: "verify", "verify.seg", "pairing", "kzg", "check"
+// and "srs.g1_ntt" (timing enabled), "seam" and "side" (hipEventDisableTiming).  Not from here, because they live and die with
+// something else: ctx->ev (made by ctx_create, read by the MSM / NTT hot path and the *_async pending flags), acc_ev (the experiment
+// streams), comm_ev (the communicator, capi_comm.hip) and CosetShare::done (the circuit).
+int ev_get(bp_ctx* ctx, const char* name, size_t count, unsigned flags, hipEvent_t** out);
 int pinned_get(bp_ctx* ctx, size_t bytes, void** out);
 
 // ---- launchers implemented in msm.hip / ntt.hip / poly.hip / srs.hip --------------------------------
@@ -360,7 +367,7 @@ int kzg_open_monomial_run(bp_ctx* ctx, const fr_t* const* d_polys, const size_t*
                           fr_t* host_y, fr_t** d_q, size_t* nq);
 
 void comm_release(bp_ctx* ctx);                 // capi_comm.hip: destroys the context's communicator, if any
-int side_ctx_get(bp_ctx* ctx, bp_ctx** out);       // creates ctx->side and its events on first use (capi_ctx.hip)
+int side_ctx_get(bp_ctx* ctx, bp_ctx** out);       // creates ctx->side on first use (capi_ctx.hip)
 int circuit_build(bp_ctx* ctx, uint32_t log_n, fr_t* d_lag, CircuitEntry* out);
 int circuit_split_build(bp_ctx* ctx, CircuitEntry& e);      // leader of a group: the members' coset shares (prover.hip)
 void circuit_release(CircuitEntry& e);

@@ -222,6 +222,7 @@ struct Prove {
   const fr_t* coefs5[5];                        // a, b, c, z, PI in coefficient form: the slots of coset_eval / coset_inputs ...
   size_t lens5[5], hi_len;                      // ... their lengths; coefficients of t_hi
   fr_t beta, gamma, alpha, zeta, nu, bar[6], pi_zeta;      // bar: a b c s1 s2 at zeta, z at zeta w (the proof's six evaluations)
+  hipEvent_t* side_ev = nullptr;                // path.side: the context's two "side" events, taken by round 1: [0] inputs ready, [1] side work done
 };
 
 // Round 3 by coset, in two parts, both on the shares' work contexts (CosetShare::work).
@@ -334,11 +335,11 @@ static int round1_staged(Prove& p) {
   const size_t n = p.n;
   BP_TRY(side_ctx_get(ctx, &sd));
   hipStream_t ss = sd->stream;
-  for (auto& e : ctx->seam_ev)
-    if (!e) BP_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipEvent_t* seam_ev;                                              // [j]: column j staged (side stream); [3] doubles as the order of the two streams
+  BP_TRY(ev_get(ctx, "seam", 4, hipEventDisableTiming, &seam_ev));
   fr_t* wit = const_cast<fr_t*>(p.d_wit);                           // the caller's "prove.witness" workspace: filled here
-  BP_HIP(ctx, hipEventRecord(ctx->seam_ev[3], ctx->stream));        // behind whatever the context's stream still holds
-  BP_HIP(ctx, hipStreamWaitEvent(ss, ctx->seam_ev[3], 0));
+  BP_HIP(ctx, hipEventRecord(seam_ev[3], ctx->stream));             // behind whatever the context's stream still holds
+  BP_HIP(ctx, hipStreamWaitEvent(ss, seam_ev[3], 0));
   MsmPending pend[3];
   int launched = 0, rc = BP_OK;
   for (int j = 0; j < 4 && rc == BP_OK; j++) {
@@ -357,12 +358,12 @@ static int round1_staged(Prove& p) {
       blind_column(p, ss, j);
       he = hipGetLastError();
     }
-    if (he == hipSuccess) he = hipEventRecord(ctx->seam_ev[j], ss);
+    if (he == hipSuccess) he = hipEventRecord(seam_ev[j], ss);
     if (he != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "round 1: staging of a witness column", he, __FILE__, __LINE__);
-    else if (j < 3 && (rc = commit_lane_launch(ctx, j, p.srs, p.abc[j], n + 2, ctx->seam_ev[j], &pend[j])) == BP_OK) launched = j + 1;
+    else if (j < 3 && (rc = commit_lane_launch(ctx, j, p.srs, p.abc[j], n + 2, seam_ev[j], &pend[j])) == BP_OK) launched = j + 1;
   }
   if (rc == BP_OK) {                                                // rounds 2.. read the columns and coefficients on the context's stream
-    const hipError_t he = hipStreamWaitEvent(ctx->stream, ctx->seam_ev[3], 0);
+    const hipError_t he = hipStreamWaitEvent(ctx->stream, seam_ev[3], 0);
     if (he != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "round 1: order", he, __FILE__, __LINE__);
   }
   for (int j = 0; j < launched; j++) {                              // every launched lane is waited for, also after a failure
@@ -389,10 +390,11 @@ static int round1(Prove& p) {
   // and the host's transcript steps.  Round 3 waits for the second event and transforms z alone.  (When: prover_host.hpp, prove_paths.)
   if (p.path.side) {
     BP_TRY(side_ctx_get(ctx, &side));
-    BP_HIP(ctx, hipEventRecord(ctx->side_ev[0], ctx->stream));
-    BP_HIP(ctx, hipStreamWaitEvent(side->stream, ctx->side_ev[0], 0));
+    BP_TRY(ev_get(ctx, "side", 2, hipEventDisableTiming, &p.side_ev));
+    BP_HIP(ctx, hipEventRecord(p.side_ev[0], ctx->stream));
+    BP_HIP(ctx, hipStreamWaitEvent(side->stream, p.side_ev[0], 0));
     BP_TRY(lift(ctx, side, coset_eval(side, p.cir, p.coefs5, p.lens5, p.pi_zero ? 0x07u : 0x17u, p.pi_zero, p.ev)));
-    BP_HIP(ctx, hipEventRecord(ctx->side_ev[1], side->stream));
+    BP_HIP(ctx, hipEventRecord(p.side_ev[1], side->stream));
   }
   host_compress48_many(p.proof, &p.cm[0], 3);    // compressed once, into the proof; the transcript absorbs the same 48 bytes (transcript.rs:66-69)
   p.tr.point48("a_1", p.proof); p.tr.point48("b_1", p.proof + 48); p.tr.point48("c_1", p.proof + 96);
@@ -425,7 +427,7 @@ static int round3_whole_coset(Prove& p) {
   const size_t N = 4 * p.n;
   if (p.path.side) {
     BP_TRY(coset_eval(ctx, p.cir, p.coefs5, p.lens5, 0x08u, false, p.ev));           // z alone ...
-    BP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[1], 0));                // ... a, b, c, PI: transformed beside rounds 1-2
+    BP_HIP(ctx, hipStreamWaitEvent(ctx->stream, p.side_ev[1], 0));                // ... a, b, c, PI: transformed beside rounds 1-2
   } else {
     BP_TRY(coset_eval(ctx, p.cir, p.coefs5, p.lens5, p.pi_zero ? 0x0Fu : 0x1Fu, p.pi_zero, p.ev));
   }

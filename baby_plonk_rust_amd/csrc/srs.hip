@@ -106,15 +106,8 @@ int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t
 
 // d_out[i] = (i_ntt_381 over G1 of d_in[0 .. 2^log_n))_i, affine: log_n passes of g1_ntt_pass over two projective buffers (pass 0
 // reads d_in itself: lift, bit reversal and the n^-1 scaling are part of it), then the shared-inversion normalisation every
-// projective SRS load goes through.  Enqueued on ctx->stream and waited for: the pass times (HIP events) are read before it returns.
-namespace {
-struct PassEvents {
-  std::vector<hipEvent_t> ev;
-  ~PassEvents() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
+// projective SRS load goes through.  Enqueued on ctx->stream and waited for: the pass times (the context's "srs.g1_ntt" events, one
+// more than the longest transform so far has passes) are read before it returns.
 int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_out) {
   ctx->g1_ntt_pass_ms.clear();
   if (log_n > G1_NTT_MAX_LOG) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "G1 transform longer than 2^24");
@@ -133,26 +126,22 @@ int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_
   (void)host_root_of_unity(omega, (uint64_t)n);
   Fr::from_mont(n_inv, n_inv);
   BP_TRY(roots_run(ctx, omega, half, tw));             // omega_n^k, k < n / 2
-  PassEvents pe;
-  for (uint32_t i = 0; i <= log_n; i++) {
-    hipEvent_t e;
-    BP_HIP(ctx, hipEventCreate(&e));
-    pe.ev.push_back(e);
-  }
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "srs.g1_ntt", log_n + 1, hipEventDefault, &ev));
   const dim3 grid((unsigned)((half + 255) / 256));
-  BP_HIP(ctx, hipEventRecord(pe.ev[0], ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
   for (uint32_t s = 0; s < log_n; s++) {
     if (s == 0) hipLaunchKernelGGL(g1_ntt_pass<true>, grid, dim3(256), 0, ctx->stream, log_n, s, d_in, (const g1_proj*)nullptr, dst, tw, n_inv);
     else hipLaunchKernelGGL(g1_ntt_pass<false>, grid, dim3(256), 0, ctx->stream, log_n, s, (const g1_affine*)nullptr, src, dst, tw, n_inv);
     BP_HIP(ctx, hipGetLastError());
-    BP_HIP(ctx, hipEventRecord(pe.ev[s + 1], ctx->stream));
+    BP_HIP(ctx, hipEventRecord(ev[s + 1], ctx->stream));
     std::swap(src, dst);
   }
   BP_TRY(srs_from_projective_run(ctx, src, n, d_out));
   BP_HIP(ctx, stream_wait(ctx->stream));
   for (uint32_t s = 0; s < log_n; s++) {
     float ms = 0;
-    BP_HIP(ctx, hipEventElapsedTime(&ms, pe.ev[s], pe.ev[s + 1]));
+    BP_HIP(ctx, hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
     ctx->g1_ntt_pass_ms.push_back(ms);
   }
   return BP_OK;

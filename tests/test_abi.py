@@ -29,6 +29,24 @@ def test_library_exports_every_header_symbol():
     assert sorted(_lib.SIGNATURES) == names          # python binding table and header agree
 
 
+# the only exported names the header does not declare: the hooks of tests/test_gpu_msm_tables.py and tools/srs_lagrange_timing.py
+HOOKS = ["bpx_set_free_bytes_probe", "bpx_srs_lagrange_pass_ms"]
+
+
+def test_library_exports_nothing_but_the_header_and_the_hooks():
+    """csrc/exports.map: the object is linked into a Rust binary beside other native code, so no helper, kernel handle or template
+    instantiation of its own may be visible -- for the shipped library and for the experiment build where it exists"""
+    import subprocess
+    here = os.path.join(ROOT, "baby_plonk_rust_amd")
+    for so in ("libbp_msm_ntt.so", "libbp_msm_ntt_exp.so"):
+        path = os.path.join(here, so)
+        if so.endswith("_exp.so") and not os.path.exists(path):
+            continue
+        listing = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        names = sorted(line.split()[-1] for line in listing.splitlines() if line.strip())
+        assert names == sorted(header_symbols() + HOOKS), (so, sorted(set(names) ^ set(header_symbols() + HOOKS)))
+
+
 def test_rust_bindings_follow_the_header():
     """include/bp_msm_ntt.rs (the extern "C" block a maintainer of the Rust reference drops in as src/gpu.rs) is
     generated from the header: it is current, declares every entry point, and its arity agrees with the ctypes table the parity

@@ -202,32 +202,7 @@ int ctx_create(bp_ctx** out, int device_id) {
   if (hipGetDevice(&cur) != hipSuccess || cur != device_id) return BP_ERR_NO_DEVICE;
   bp_ctx* ctx = new bp_ctx();
   ctx->device = device_id;
-  hipError_t se;
-  if (const uint32_t keep = knob_u32("BP_ACC_CU_KEEP", 0, 1, 31)) {
-    // experiment: msm_accumulate on a stream whose CU mask leaves one CU in every (keep + 1) free for the other streams' kernels (a
-    // RESERVATION, where priorities and generations only reorder what waits): hipExtStreamCreateWithCUMask, thinning pattern repeated
-    // over 320 mask bits so that it does not depend on how the runtime numbers the CUs of the 8 XCDs
-    uint32_t mask[10];
-    for (int w = 0; w < 10; w++) {
-      mask[w] = 0;
-      for (int b = 0; b < 32; b++)
-        if ((uint32_t)(w * 32 + b) % (keep + 1) != keep) mask[w] |= 1u << b;
-    }
-    se = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (se == hipSuccess) se = hipExtStreamCreateWithCUMask(&ctx->acc_stream, 10, mask);
-    for (auto& e : ctx->acc_ev)
-      if (se == hipSuccess) se = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  } else if (knob_u32("BP_ACC_LOW_PRIORITY", 0, 0, 1)) {         // experiment: tails on high-priority streams, accumulations on low-priority ones
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = least urgent (numerically greatest), hi = most urgent
-    se = hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, hi);
-    if (se == hipSuccess) se = hipStreamCreateWithPriority(&ctx->acc_stream, hipStreamNonBlocking, lo);
-    for (auto& e : ctx->acc_ev)
-      if (se == hipSuccess) se = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  } else {
-    se = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  }
-  if (se != hipSuccess) {
+  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     delete ctx;
     return BP_ERR_NO_DEVICE;
   }
@@ -364,9 +339,6 @@ void bp_destroy(bp_ctx* ctx) {
     if (t) (void)hipFree(t);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->acc_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->acc_stream) (void)hipStreamDestroy(ctx->acc_stream);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

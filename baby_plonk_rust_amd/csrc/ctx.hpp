@@ -19,7 +19,7 @@ namespace bp {
 // Experiment knobs.  The shipped library reads NO environment variable: every default is the measured best and nothing in the
 // embedding process's environment can change a kernel shape.  A build with -DBP_EXPERIMENT (`make exp` -> libbp_msm_ntt_exp.so,
 // loaded by the tests under tests/ that are marked `experiment`, and by the A/B tools) reads the BP_* variables of DESIGN.md
-// section 12, compiles the alternative builds they select (the one-histogram counting sort, every-position NAF tables) and
+// section 12, compiles the alternative build they select (every-position NAF tables) and
 // honours the test hook BP_FORCE_PEER_COPIES.
 #ifdef BP_EXPERIMENT
 inline const char* knob(const char* name) { return getenv(name); }
@@ -148,11 +148,6 @@ struct bp_ctx {
   std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  // experiment (BP_ACC_LOW_PRIORITY=1): msm_accumulate runs on a lowest-priority stream of its own, chained to `stream` by
-  // events, while `stream` is created at the highest priority -- so that sort / fix-up / tree kernels of OTHER pipelines take the
-  // workgroup slots a retiring accumulation generation frees.  Measured: profiles/r05_accumulate_generations_ab.txt.
-  hipStream_t acc_stream = nullptr;
-  hipEvent_t acc_ev[2] = {nullptr, nullptr};
   std::string last_error;
   std::map<std::string, bp::DevBuf> ws;            // grow-only named device workspaces (ws_get)
   std::map<std::string, std::vector<hipEvent_t>> events;      // grow-only named sets of HIP events (ev_get)
@@ -171,7 +166,7 @@ struct bp_ctx {
   uint32_t msm_c = 0;
   bool msm_tables = false;
   // what the last msm_launch_many that enqueued a pipeline on THIS context decided (bp_msm_last_path): J, c, W, radix, sort (1 two-level,
-  // 2 partition; 0 the experiment build's counting sort), pb, packed, flat, wide8, fixup (0 per bucket, 1 per edge), n_wide, chunk
+  // 2 partition), pb, packed, flat, wide8, fixup (0 per bucket, 1 per edge), n_wide, chunk
   uint32_t msm_path[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float prove_ms[6] = {0, 0, 0, 0, 0, 0};            // host wall clock of rounds 1..5 and of the whole bp_prove
   float check_ms[3] = {0, 0, 0};                     // last bp_circuit_check_*: sigma decode (0: cached), upload + conversion, the check kernel
@@ -280,8 +275,7 @@ int ws_get(bp_ctx* ctx, const char* name, size_t bytes, void** out);
 // valid until the next ev_get of the same name (a larger count may move the set).  Every event an entry point records to time its
 // stages or to order the context's stream against the side stream comes from here: "verify", "verify.seg", "pairing", "kzg", "check"
 // and "srs.g1_ntt" (timing enabled), "seam" and "side" (hipEventDisableTiming).  Not from here, because they live and die with
-// something else: ctx->ev (made by ctx_create, read by the MSM / NTT hot path and the *_async pending flags), acc_ev (the experiment
-// streams), comm_ev (the communicator, capi_comm.hip) and CosetShare::done (the circuit).
+// something else: ctx->ev (made by ctx_create, read by the MSM / NTT hot path and the *_async pending flags), comm_ev (the communicator, capi_comm.hip) and CosetShare::done (the circuit).
 int ev_get(bp_ctx* ctx, const char* name, size_t count, unsigned flags, hipEvent_t** out);
 int pinned_get(bp_ctx* ctx, size_t bytes, void** out);
 

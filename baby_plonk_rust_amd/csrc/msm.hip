@@ -62,8 +62,6 @@ static void make_plan(MsmPlan& plan, size_t n, uint32_t table_c, size_t table_st
     if (chunk > 1024) chunk = 1024;
     plan.chunk = knob_u32("BP_MSM_CHUNK", chunk, 1, 1024);
     plan.lanes = knob_u32("BP_MSM_CHUNK", 0, 1, 1024) ? 0u : (uint32_t)(((uint64_t)plan.W * n * J + plan.chunk - 1) / plan.chunk);
-    plan.slices = 1;
-    plan.seg = 1;
     return;
   }
   uint32_t c = n < 32 ? 4 : ilog2_floor(n) - 3;
@@ -142,17 +140,6 @@ static void make_plan(MsmPlan& plan, size_t n, uint32_t table_c, size_t table_st
   if (chunk > chunk_cap) chunk = chunk_cap;
   plan.chunk = knob_u32("BP_MSM_CHUNK", chunk, 1, 1024);
   plan.lanes = knob_u32("BP_MSM_CHUNK", 0, 1, 1024) ? 0u : (uint32_t)((entries + plan.chunk - 1) / plan.chunk);      // = the host's n_chunks
-  // count/scatter workgroups per window: each flushes its whole LDS histogram with global atomics, so fewer, fatter
-  // slices are cheaper (~32 Ki points each) as long as >= 256 workgroups remain to fill the CUs (measured: 2^16, 2^20, 2^24)
-  uint32_t slices = (uint32_t)(n >> 15), lo = 256 / W, hi = 1024 / W;
-  if (slices < lo) slices = lo;
-  if (slices > hi) slices = hi;
-  if (slices < 1) slices = 1;
-  while (slices > 1 && n / slices < 1024) slices >>= 1;
-  plan.slices = knob_u32("BP_MSM_SLICES", slices, 1, 4096);
-  uint32_t seg = 1;
-  while (seg < 32 && plan.total / seg > 65536) seg <<= 1;
-  plan.seg = knob_u32("BP_MSM_SEG", seg, 1, 1024);
 }
 
 // unsaturated copy of an SRS (128-byte slots) (allocated here, owned by the SRS entry)
@@ -215,11 +202,6 @@ static g1_proj slot_to_proj(const proj28_slot* slot) {
 
 // dynamic-LDS limits are per function AND per device: set them for every context at creation (bp_init), after hipSetDevice
 int msm_init_device(bp_ctx* ctx) {
-  // a full-window histogram at c = 16 needs 128 KiB of dynamic LDS
-#ifdef BP_EXPERIMENT
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_count, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
   // these two also hold a few KiB of static LDS: the dynamic limit must leave room for it
   BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
   BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_final<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
@@ -233,6 +215,33 @@ int msm_init_device(bp_ctx* ctx) {
   BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
   BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
   return BP_OK;
+}
+
+// scalars per workgroup of a pass that cuts digits from the scalars: `slice` doubled up to `limit` while that leaves at least `wgs` workgroups
+// and the pass's staging area (`staged` bytes per scalar, twice) stays within 64 KiB
+static uint32_t part_slice(uint32_t slice, uint32_t limit, uint32_t wgs, uint64_t scalars, uint64_t staged) {
+  while (slice < limit && 2 * slice * staged <= 65536 && (uint64_t)slice * wgs < scalars) slice <<= 1;
+  return slice;
+}
+
+// the partition sort behind its count pass, for one record form: the scatter, the final runs, the long runs among them
+template <bool PACKED>
+static void part_sort_launch(hipStream_t st, bool flat, uint32_t n_slices, unsigned threads, size_t part_lds, unsigned final_threads, size_t rhist,
+                             const MsmScalars& scalars, int fmt, const MsmPlan& plan, uint32_t slice, uint32_t pb, uint32_t rbits, uint32_t vb, uint32_t cap,
+                             uint32_t* cur, uint32_t* recs, uint32_t* rvals, uint32_t* roff, uint32_t* offsets, uint32_t* sorted, uint32_t* rlong_n,
+                             uint32_t* rlong_list, uint32_t* counts, uint32_t* cursors, uint32_t* run_ticket) {
+  const uint32_t n_final = 1u << pb, total = plan.total;
+  if (flat) hipLaunchKernelGGL((msm_part_scatter<PACKED, true>), dim3(n_slices), dim3(threads), part_lds, st, scalars, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
+  else hipLaunchKernelGGL((msm_part_scatter<PACKED, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
+  const RunRecords<PACKED> rr{recs, rvals, (1u << rbits) - 1u, PACKED ? vb : 0u};       // rvals: null with packed records
+  hipLaunchKernelGGL(msm_radix_final<PACKED>, dim3(n_final < 4096 ? n_final : 4096), dim3(final_threads), rhist, st, rr, roff, n_final, rbits, total, offsets,
+                     sorted, rlong_n, rlong_list, counts);
+  if (n_final > 1) {
+    const dim3 lgrid(64, n_final < 4 ? n_final : 4);
+    hipLaunchKernelGGL(msm_radix_long_count<PACKED>, lgrid, dim3(1024), rhist, st, rr, roff, n_final, rbits, total, rlong_n, rlong_list, counts, offsets,
+                       cursors, run_ticket);
+    hipLaunchKernelGGL(msm_radix_long_scatter<PACKED>, lgrid, dim3(1024), rhist, st, rr, roff, rbits, rlong_n, rlong_list, cursors, sorted);
+  }
 }
 
 // d_points28: the unsaturated SRS copy, or (table_c != 0) row 0 of its fixed-base tables with rows table_stride apart.
@@ -252,9 +261,6 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "MSM batch");
   size_t n = 0;
   for (uint32_t j = 0; j < J; j++) n = n_each[j] > n ? n_each[j] : n;
-#ifdef BP_EXPERIMENT
-  const fr_t* d_scalars = d_scalars_each[0];           // the records-first passes (experiment builds) take a single vector
-#endif
   out->J = J;
   if (n == 0) {
     if (d_blob) {
@@ -277,22 +283,17 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   }
   if ((uint64_t)plan.W * n * J >= (1ull << 32))        // positions in the bucket-sorted list are 32-bit
     return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM length * windows >= 2^32");
-  const uint32_t W = plan.W, B = plan.B, total = plan.total, Wr = table_c ? J : W;   // Wr: bucket sets left after accumulation
+  const uint32_t W = plan.W, total = plan.total, Wr = table_c ? J : W;   // Wr: bucket sets left after accumulation
   const uint64_t max_entries = (uint64_t)W * n * J;
   const uint64_t n_chunks = (max_entries + plan.chunk - 1) / plan.chunk;
-  // bucket reduction: the bit-plane tree over one bucket set (tables) or over the forest of W bucket sets (table-free); the running sums per
-  // window of rounds 1-4 (msm_reduce: blocks_per_window, plan.seg) exist in the experiment build only (BP_MSM_REDUCE=1)
-  const uint32_t blocks_per_window = (!EXPERIMENT_BUILD || table_c) ? 0 : ((B + plan.seg - 1) / plan.seg + 255) / 256;
-  // Bucket reduction without tables (W bucket sets of 2^(c-1) buckets): the same bit-plane tree as with tables, over a forest of W trees
-  // (round 5; rounds 1-4 ran segmented running sums per window, msm_reduce: a dependent chain of ~46 additions per lane, 256 VGPRs + spills,
-  // 0.57 ms at 2^20 points -- kept in the experiment build as BP_MSM_REDUCE=1 for the A/B), then two levels of the Horner form over each
-  // tree's c values (msm_planes_window_quads): `quads` values per window go to the host.
-  const bool reduce_running = EXPERIMENT_BUILD && !table_c && knob_u32("BP_MSM_REDUCE", 0, 0, 1) == 1;
-  const uint32_t quads = (table_c || reduce_running) ? 1u : (plan.c + 2) / 4;          // ceil((c - 1) / 4); c = 2: one quad (A + T_0)
+  // Bucket reduction: the bit-plane tree over one bucket set (tables) or, without tables, over the forest of the W bucket sets of 2^(c-1)
+  // buckets (running sums per window, a dependent chain of ~46 additions per lane, cost 0.57 ms at 2^20 points: docs/EXPERIMENTS.md Q), then
+  // two levels of the Horner form over each tree's c values (msm_planes_window_quads): `quads` values per window go to the host.
+  const uint32_t quads = table_c ? 1u : (plan.c + 2) / 4;          // ceil((c - 1) / 4); c = 2: one quad (A + T_0)
   const uint32_t per_window = table_c ? plan.c : quads;     // slots per window that go to the host
 
   uint32_t *counts, *offsets, *cursors, *sorted;
-  proj28_slot *bucket_sum, *partial, *block_out, *window_sum;
+  proj28_slot *bucket_sum, *partial, *window_sum;
   // a bucket is "long" when it spans >= FIXUP_LONG chunks, so at most n_chunks / FIXUP_LONG + 1 buckets can be long
   const uint32_t long_cap = (uint32_t)(n_chunks / FIXUP_LONG + 1);
   // control words, zeroed by ONE memset per MSM: [0] long-bucket counter, [1] scalar status, [2] long-run counter of the sort,
@@ -302,7 +303,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   const size_t ctl_fixed = 8 + PART_MAX + long_cap;
   BP_TRY(ws_get(ctx, "msm.ctl", (ctl_fixed + 65536) * 4, (void**)&ctl));
   uint32_t* run_ticket = ctl + ctl_fixed;
-  BP_TRY(ws_get(ctx, "msm.counts", (size_t)total * 4, (void**)&counts));        // bucket sizes (histogram sort; long runs of the other two)
+  BP_TRY(ws_get(ctx, "msm.counts", (size_t)total * 4, (void**)&counts));        // bucket sizes of the sort's long runs
   BP_TRY(ws_get(ctx, "msm.offsets", ((size_t)total + 1) * 4, (void**)&offsets));
   BP_TRY(ws_get(ctx, "msm.cursors", (size_t)total * 4, (void**)&cursors));
   uint32_t *long_count = ctl, *long_list, *long_ticket = ctl + 8 + PART_MAX;
@@ -318,10 +319,8 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   BP_TRY(ws_get(ctx, "msm.partial", 2 * n_chunks * sizeof(proj28_slot), (void**)&partial));
   const uint32_t n_planes = Wr * per_window;        // tables: A and the c - 1 bit planes; else one sum per window
   if (n_planes > (uint32_t)MSM_MAX_WINDOWS) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM windows");
-  block_out = nullptr;
-  if (reduce_running) BP_TRY(ws_get(ctx, "msm.block_out", (size_t)Wr * blocks_per_window * sizeof(proj28_slot), (void**)&block_out));
   proj28_slot* roots = nullptr;                     // table-free: the W roots (A, T_0 .. T_{c-2}) in front of the per-window Horner pass
-  if (!table_c && !reduce_running) BP_TRY(ws_get(ctx, "msm.roots", (size_t)W * plan.c * sizeof(proj28_slot), (void**)&roots));
+  if (!table_c) BP_TRY(ws_get(ctx, "msm.roots", (size_t)W * plan.c * sizeof(proj28_slot), (void**)&roots));
   BP_TRY(ws_get(ctx, "msm.window_sum", (size_t)n_planes * sizeof(proj28_slot) + 16, (void**)&window_sum));     // + the status word
   // pinned staging: MSM_SLOTS result areas of the largest possible size, so earlier pending results stay where they are
   constexpr size_t slot_bytes = (size_t)MSM_MAX_WINDOWS * sizeof(proj28_slot) + 16;
@@ -330,9 +329,8 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   proj28_slot* h_windows = reinterpret_cast<proj28_slot*>(h_base + (size_t)slot * slot_bytes);
   hipStream_t st = ctx->stream;
   BP_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  // Bucket sort, three builds: the partition sort (default wherever its 2^pb <= 2^11 partitions leave final runs
-  // that one workgroup sorts: up to ~5 * 10^7 entries), the two-level radix sort (beyond), the one-histogram counting sort of
-  // round 1 (c <= 16 only; kept selectable for A/B: BP_MSM_SORT=0 histogram, 1 two-level, 2 partition).
+  // Bucket sort, two builds: the partition sort (default wherever its 2^pb <= 2^11 partitions leave final runs
+  // that one workgroup sorts: up to ~5 * 10^7 entries) and the two-level radix sort (beyond; BP_MSM_SORT=1 forces it, 2 is the default).
   uint32_t kb = 0;
   while ((1ull << kb) < total) kb++;
   uint32_t pb = 0;
@@ -354,9 +352,8 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   while ((idx_max >> (vb - 1)) != 0) vb++;                              // vb - 1 = bits of the largest entry, + 1 for the sign
   const uint32_t packed_env = knob_u32("BP_MSM_PACKED", 1, 0, 2);
   if (packed_env == 1 && kb + vb > 32 + pb && kb + vb - 32 <= PART_MAX_BITS && knob_u32("BP_MSM_RADIX_BITS", 99, 0, 16) == 99) pb = kb + vb - 32;
-  const uint32_t sort_env = knob_u32("BP_MSM_SORT", 2, 0, 3);      // 3: the two-level sort (first level from the scalars) at sizes where the partition sort is the default
-  const bool hist_ok = plan.parts == 1 && !plan.naf && J == 1;
-  const int sort_mode = (EXPERIMENT_BUILD && sort_env == 0 && hist_ok) ? 0 : ((((sort_env == 1 || sort_env == 3) && J == 1) || pb > PART_MAX_BITS) ? 1 : 2);
+  // 1: the two-level sort.  BP_MSM_SORT=1 takes it at sizes where the partition sort is the default (pb = 0 leaves no level to sort by: ignored)
+  const int sort_mode = ((knob_u32("BP_MSM_SORT", 2, 1, 2) == 1 && J == 1 && pb > 0) || pb > PART_MAX_BITS) ? 1 : 2;
   if (sort_mode != 2 && J > 1) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM batch too long for the partition sort");
   const uint32_t rbits = kb - pb, n_final = 1u << pb;
   // what this launch decided (bp_msm_last_path): host words only, copied into the context once everything is enqueued
@@ -368,8 +365,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     const bool packed = rbits + vb <= 32 && packed_env != 0;
     const uint32_t rec_bytes = packed ? 4 : 8;
     // scalars per workgroup: the staging area (slice * W records) within 64 KiB, and >= 512 workgroups where n allows
-    uint32_t slice = 64;
-    while (slice < 1024 && (uint64_t)2 * slice * W * rec_bytes <= 65536 && (uint64_t)slice * 512 < (uint64_t)n * J) slice <<= 1;
+    uint32_t slice = part_slice(64, 1024, 512, (uint64_t)n * J, (uint64_t)W * rec_bytes);
     slice = knob_u32("BP_MSM_PART_SLICE", slice, 64, 4096);
     if (slice < 64 || slice > 4096 || (uint64_t)slice * W * rec_bytes > 65536) slice = 64;
     // Two-word records (2^21 .. 2^23 points at c = 20: bucket-low bits + sign + a 25..27-bit table index exceed one word): the 64-KiB rule leaves
@@ -389,8 +385,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     BP_TRY(ws_get(ctx, "msm.run_long", ((size_t)n_final + 2) * 4, (void**)&rlong_list));
     // the count pass keeps nothing per slice, so its slices are its own: fatter ones (~256 workgroups) flush their 2^pb partition
     // sizes with a quarter of the global atomics (BP_MSM_COUNT_SLICE forces a size)
-    uint32_t slice1 = slice;
-    while (slice1 < 8192 && (uint64_t)slice1 * 256 < (uint64_t)n * J) slice1 <<= 1;      // measured at 2^20: 48 / 41 / 34 / 48 us at 1 024 / 2 048 / 4 096 / 8 192
+    uint32_t slice1 = part_slice(slice, 8192, 256, (uint64_t)n * J, 0);      // measured at 2^20: 48 / 41 / 34 / 48 us at 1 024 / 2 048 / 4 096 / 8 192
     slice1 = knob_u32("BP_MSM_COUNT_SLICE", slice1, 64, 65536);
     const uint32_t n_slices1 = (uint32_t)(((uint64_t)n * J + slice1 - 1) / slice1);
     hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb, rbits, ctl + 4, roff, cur, long_count + 1);
@@ -401,32 +396,10 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     path[6] = packed;
     path[7] = flat;
     path[8] = wide8;
-    const dim3 lgrid(64, n_final < 4 ? n_final : 4);
     // short final runs (2^12 runs of ~3 Ki records at c = 20): 512-lane workgroups (measured 70 / 60 / 72 us at 256 / 512 / 1024 lanes)
     const unsigned final_threads = knob_u32("BP_MSM_FINAL_THREADS", (max_entries >> pb) <= 8192 ? 512 : 1024, 256, 1024) & ~63u;
-    if (packed) {
-      if (flat) hipLaunchKernelGGL((msm_part_scatter<true, true>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-      else hipLaunchKernelGGL((msm_part_scatter<true, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-      const RunRecords<true> rr{recs, nullptr, (1u << rbits) - 1u, vb};
-      hipLaunchKernelGGL(msm_radix_final<true>, dim3(n_final < 4096 ? n_final : 4096), dim3(final_threads), rhist, st, rr, roff, n_final, rbits, total, offsets,
-                         sorted, rlong_n, rlong_list, counts);
-      if (n_final > 1) {
-        hipLaunchKernelGGL(msm_radix_long_count<true>, lgrid, dim3(1024), rhist, st, rr, roff, n_final, rbits, total, rlong_n, rlong_list, counts, offsets,
-                           cursors, run_ticket);
-        hipLaunchKernelGGL(msm_radix_long_scatter<true>, lgrid, dim3(1024), rhist, st, rr, roff, rbits, rlong_n, rlong_list, cursors, sorted);
-      }
-    } else {
-      if (flat) hipLaunchKernelGGL((msm_part_scatter<false, true>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-      else hipLaunchKernelGGL((msm_part_scatter<false, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-      const RunRecords<false> rr{recs, rvals, (1u << rbits) - 1u, 0u};
-      hipLaunchKernelGGL(msm_radix_final<false>, dim3(n_final < 4096 ? n_final : 4096), dim3(final_threads), rhist, st, rr, roff, n_final, rbits, total, offsets,
-                         sorted, rlong_n, rlong_list, counts);
-      if (n_final > 1) {
-        hipLaunchKernelGGL(msm_radix_long_count<false>, lgrid, dim3(1024), rhist, st, rr, roff, n_final, rbits, total, rlong_n, rlong_list, counts, offsets,
-                           cursors, run_ticket);
-        hipLaunchKernelGGL(msm_radix_long_scatter<false>, lgrid, dim3(1024), rhist, st, rr, roff, rbits, rlong_n, rlong_list, cursors, sorted);
-      }
-    }
+    (packed ? part_sort_launch<true> : part_sort_launch<false>)(st, flat, n_slices, threads, part_lds, final_threads, rhist, scalars_all, fmt, plan, slice, pb, rbits,
+                                                               vb, cap, cur, recs, rvals, roff, offsets, sorted, rlong_n, rlong_list, counts, cursors, run_ticket);
   } else if (sort_mode == 1) {
     const uint32_t lv[2] = {pb <= 8 ? pb : pb - pb / 2, pb <= 8 ? 0 : pb / 2};
     uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *run_off[3], *cnt, *cur;
@@ -447,21 +420,16 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     BP_HIP(ctx, hipMemcpyAsync(run_off[0], whole, sizeof whole, hipMemcpyHostToDevice, st));
     uint32_t* rlong_list;
     BP_TRY(ws_get(ctx, "msm.run_long", ((size_t)n_final + 2) * 4, (void**)&rlong_list));
-    // Level 1 of the two-level sort, two builds.  Straight from the scalars, as the partition sort does it (msm_part_count + msm_part_scatter
-    // with two-word records into 2^lv[0] runs: no record pass, one array's traffic less -- the default since round 4: 2^24 points, tail
-    // 5.87 -> 5.32 ms, profiles/r04_sort24_hybrid_ab.txt), or records first (msm_digit_records writes one (bucket, entry) pair per scalar and
-    // window, then msm_radix_count / _scatter partition them: a single level, NAF digits, or BP_MSM_SORT=1 in the experiment build).
+    // Level 1 comes straight from the scalars, as the partition sort does it (msm_part_count + msm_part_scatter with two-word records into
+    // 2^lv[0] runs: no record pass, one array's traffic less -- 2^24 points, tail 5.87 -> 5.32 ms, profiles/r04_sort24_hybrid_ab.txt).  NAF
+    // digits (experiment build) are written as records first (msm_naf_records) and partitioned by msm_radix_count / _scatter at both levels.
     uint32_t runs = 1, shift = kb, side = 0;
     int first_level = 0;
-    const bool hybrid = sort_env != 1 && lv[0] && lv[1] && !plan.naf;
-    if (hybrid) {
+    if (!plan.naf) {
       const uint32_t pb1 = lv[0], rb1 = kb - pb1;
-      uint32_t slice = 64;
-      while (slice < 1024 && (uint64_t)2 * slice * W * 8 <= 65536 && (uint64_t)slice * 512 < (uint64_t)n) slice <<= 1;
+      const uint32_t slice = part_slice(64, 1024, 512, n, (uint64_t)W * 8), slice1 = part_slice(slice, 8192, 256, n, 0);
       const uint32_t cap = slice * W, n_slices = (uint32_t)(((uint64_t)n + slice - 1) / slice);
       const unsigned threads = slice >= 1024 ? 1024u : (slice <= 256 ? 256u : slice);
-      uint32_t slice1 = slice;
-      while (slice1 < 8192 && (uint64_t)slice1 * 256 < (uint64_t)n) slice1 <<= 1;
       const uint32_t n_slices1 = (uint32_t)(((uint64_t)n + slice1 - 1) / slice1);
       hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb1, rb1, ctl + 4, run_off[1], cur,
                          long_count + 1);
@@ -474,12 +442,9 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
       first_level = 1;
     } else {
 #ifdef BP_EXPERIMENT
-    if (plan.naf)
-      hipLaunchKernelGGL(msm_naf_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, fmt, plan, keys[0], vals[0], long_count + 1);
-    else
-      hipLaunchKernelGGL(msm_digit_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, fmt, plan, keys[0], vals[0], long_count + 1);
+      hipLaunchKernelGGL(msm_naf_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars_each[0], fmt, plan, keys[0], vals[0], long_count + 1);
 #else
-    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "records-first sort is an experiment build");      // unreachable: two levels always take level 1 from the scalars
+      return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NAF tables are an experiment build");      // unreachable: bp_srs_precompute refuses them in this build
 #endif
     }
     for (int level = first_level; level < 2 && lv[level]; level++) {
@@ -509,43 +474,10 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
                          offsets, cursors, run_ticket);
       hipLaunchKernelGGL(msm_radix_long_scatter<false>, lgrid, dim3(1024), rhist, st, rr, run_off[level_count], rbits, rlong_n, rlong_list, cursors, sorted);
     }
-  } else {
-#ifdef BP_EXPERIMENT
-    int16_t* digits = nullptr;
-  const size_t hist_bytes = (size_t)B * 4;
-  const unsigned hist_threads = B >= 4096 ? 1024 : 256;   // a big histogram owns the CU's LDS: fill the CU with one workgroup
-  const uint32_t n_tiles = (total + SCAN_TILE - 1) / SCAN_TILE;      // <= 4096 (total <= 2^24)
-    BP_TRY(ws_get(ctx, "msm.digits", max_entries * sizeof(int16_t), (void**)&digits));
-    BP_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)total * 4, st));
-    hipLaunchKernelGGL(msm_digits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, fmt, plan, digits, long_count + 1);
-    hipLaunchKernelGGL(msm_count, dim3(plan.slices, W), dim3(hist_threads), hist_bytes, st, digits, plan, counts);
-    hipLaunchKernelGGL(scan_tile_sums, dim3(n_tiles), dim3(256), 0, st, counts, total, tile_sums);
-    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(256), 0, st, tile_sums, n_tiles, offsets + total);
-    hipLaunchKernelGGL(scan_apply, dim3(n_tiles), dim3(256), 0, st, counts, total, tile_sums, offsets, cursors);
-    hipLaunchKernelGGL(msm_scatter, dim3(plan.slices, W), dim3(hist_threads), hist_bytes, st, digits, plan, cursors, sorted);
-#else
-    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "counting sort is an experiment build");      // unreachable: sort_mode 0 needs a knob
-#endif
   }
   BP_HIP(ctx, hipEventRecord(ctx->ev[1], st));
   const dim3 acc_grid((unsigned)((n_chunks + 255) / 256));
-  hipStream_t ast = st;
-  if (ctx->acc_stream) {                  // experiment (BP_ACC_LOW_PRIORITY): the accumulation on its low-priority stream, chained by events
-    ast = ctx->acc_stream;
-    BP_HIP(ctx, hipEventRecord(ctx->acc_ev[0], st));
-    BP_HIP(ctx, hipStreamWaitEvent(ast, ctx->acc_ev[0], 0));
-  }
-  switch (knob_u32("BP_MSM_ACC_WAVES", 2, 2, 4)) {
-#ifdef BP_EXPERIMENT          // three / four waves per SIMD: 168 / 128 VGPRs, both spill (tools/kernel_resources.py) and measured slower
-    case 3: hipLaunchKernelGGL(msm_accumulate<3>, acc_grid, dim3(256), 0, ast, d_points28, sorted, offsets, plan, bucket_sum, partial); break;
-    case 4: hipLaunchKernelGGL(msm_accumulate<4>, acc_grid, dim3(256), 0, ast, d_points28, sorted, offsets, plan, bucket_sum, partial); break;
-#endif
-    default: hipLaunchKernelGGL(msm_accumulate<2>, acc_grid, dim3(256), 0, ast, d_points28, sorted, offsets, plan, bucket_sum, partial);
-  }
-  if (ctx->acc_stream) {
-    BP_HIP(ctx, hipEventRecord(ctx->acc_ev[1], ast));
-    BP_HIP(ctx, hipStreamWaitEvent(st, ctx->acc_ev[1], 0));
-  }
+  hipLaunchKernelGGL(msm_accumulate<2>, acc_grid, dim3(256), 0, st, d_points28, sorted, offsets, plan, bucket_sum, partial);
   BP_HIP(ctx, hipEventRecord(ctx->ev[2], st));
   // fix-up of the buckets cut by chunk edges.  Long buckets (tables at c <= 17: every one of the 2^15 buckets spans several chunks):
   // two lanes per bucket = one wave per SIMD, half the chain.  Short buckets (wide windows, per-window bucket sets): most buckets
@@ -564,86 +496,71 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
                        long_cap);
   hipLaunchKernelGGL(msm_fixup_long, dim3(512), dim3(256), 256 * sizeof(proj28_slot), st, offsets, plan, bucket_sum, partial,
                      long_count, long_list, long_cap, long_scratch, long_ticket);
-  if (!reduce_running) {
-    // The tree over the `total` leaves (tables: B = 2^(c-1) buckets, J B for a batch; table-free: the forest of W trees, W B leaves),
-    // level by level.  A level with at least PLANES_WIDE_MIN additions is throughput bound: one addition per lane through HBM
-    // (msm_planes_level01 / msm_planes_level: six such levels at 2^19 leaves, seven for the table-free forest of 16 x 2^15).  The rest
-    // is latency bound: up to PLANES_STEP_LOG levels per launch inside workgroups, cooperative additions (msm_planes_step).
-    // A node of 2^k buckets carries k + 1 values; the two ping-pong buffers hold at most B values (level 1).
-    const uint32_t levels = plan.c - 1;               // >= 1 (make_plan keeps c >= 2)
-    const uint64_t wide_min = knob_u32("BP_MSM_PLANES_WIDE_MIN", 24000, 256, 1u << 30);
-    uint32_t k = 0, nodes = total, n_wide = 0;            // total = J B leaves: a forest of J trees (J > 1: the vectors of a batch)
-    while (n_wide < levels && (uint64_t)(total >> (n_wide + 1)) * (n_wide + 1) >= wide_min) n_wide++;
-    if (n_wide == levels) n_wide = levels - 1;            // the last level is always a step: it writes the result where the epilogue reads it
-    // levels 0 and 1 have the same number of additions, so a wide level 0 comes with a wide level 1 and the two run fused (msm_planes_level01);
-    // a lone wide leaf level (two-level trees, c = 3: knobs only) takes the step path in the shipped library -- its single-level LEAF kernel
-    // is the one tree kernel that spills (tools/kernel_resources.py) and lives in the experiment build only (BP_MSM_PLANES_FUSE01=0)
-    if (!EXPERIMENT_BUILD && n_wide < 2) n_wide = 0;
-    path[10] = n_wide;
-    proj28_slot* tmp[2] = {nullptr, nullptr};
-    {
-      size_t need[2] = {0, 0};
-      uint32_t kk = 0, flip = 0;
-      while (kk < levels) {
-        const uint32_t m = kk < n_wide ? 1 : (levels - kk < PLANES_STEP_LOG ? levels - kk : PLANES_STEP_LOG);
-        kk += m;
-        if (kk < levels) {
-          const size_t slots = (size_t)(total >> kk) * (kk + 1);
-          if (slots > need[flip]) need[flip] = slots;
-        }
-        flip ^= 1;
-      }
-      if (need[0]) BP_TRY(ws_get(ctx, "msm.planes_tmp0", need[0] * sizeof(proj28_slot), (void**)&tmp[0]));
-      if (need[1]) BP_TRY(ws_get(ctx, "msm.planes_tmp1", need[1] * sizeof(proj28_slot), (void**)&tmp[1]));
-    }
-    const proj28_slot* in = bucket_sum;
-    int flip = 0;
-    const bool fuse01 = n_wide >= 2 && knob_u32("BP_MSM_PLANES_FUSE01", 1, 0, 1) != 0;
-    while (k < levels) {
-      const bool leaf = k == 0;
-      if (leaf && fuse01) {                 // levels 0 and 1 in one launch, four buckets per lane
-        nodes >>= 2;
-        flip ^= 1;                          // the output takes the buffer level 1 would have taken
-        hipLaunchKernelGGL(msm_planes_level01, dim3((nodes + 255) / 256), dim3(256), 0, st, offsets, in, nodes, tmp[flip]);
-        in = tmp[flip];
-        k = 2;
-      } else if (k < n_wide) {
-        nodes >>= 1;
-        const uint64_t items = (uint64_t)nodes * (k + 1);
-        const dim3 grid((unsigned)((items + 255) / 256));
-#ifdef BP_EXPERIMENT
-        if (leaf) hipLaunchKernelGGL(msm_planes_level<true>, grid, dim3(256), 0, st, offsets, in, k, nodes, tmp[flip]);
-        else
-#endif
-        hipLaunchKernelGGL(msm_planes_level<false>, grid, dim3(256), 0, st, offsets, in, k, nodes, tmp[flip]);
-        in = tmp[flip];
-        k += 1;
-      } else {
-        const uint32_t m = levels - k < PLANES_STEP_LOG ? levels - k : PLANES_STEP_LOG;
-        nodes >>= m;
-        const bool last = k + m == levels;
-        proj28_slot* out_nodes = last ? (table_c ? window_sum : roots) : tmp[flip];
-        uint32_t* status_out = last && table_c ? reinterpret_cast<uint32_t*>(window_sum + n_planes) : (uint32_t*)nullptr;
-        const dim3 grid(nodes, k + 1);
-        const size_t lds = ((size_t)2 << m) * sizeof(proj28_slot);
-        if (leaf) hipLaunchKernelGGL(msm_planes_step<true>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
-        else hipLaunchKernelGGL(msm_planes_step<false>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
-        in = out_nodes;
-        k += m;
+  // The tree over the `total` leaves (tables: B = 2^(c-1) buckets, J B for a batch; table-free: the forest of W trees, W B leaves),
+  // level by level.  A level with at least PLANES_WIDE_MIN additions is throughput bound: one addition per lane through HBM
+  // (msm_planes_level01 / msm_planes_level: six such levels at 2^19 leaves, seven for the table-free forest of 16 x 2^15).  The rest
+  // is latency bound: up to PLANES_STEP_LOG levels per launch inside workgroups, cooperative additions (msm_planes_step).
+  // A node of 2^k buckets carries k + 1 values; the two ping-pong buffers hold at most B values (level 1).
+  const uint32_t levels = plan.c - 1;               // >= 1 (make_plan keeps c >= 2)
+  const uint64_t wide_min = knob_u32("BP_MSM_PLANES_WIDE_MIN", 24000, 256, 1u << 30);
+  uint32_t k = 0, nodes = total, n_wide = 0;            // total = J B leaves: a forest of J trees (J > 1: the vectors of a batch)
+  while (n_wide < levels && (uint64_t)(total >> (n_wide + 1)) * (n_wide + 1) >= wide_min) n_wide++;
+  if (n_wide == levels) n_wide = levels - 1;            // the last level is always a step: it writes the result where the epilogue reads it
+  // levels 0 and 1 have the same number of additions, so a wide level 0 comes with a wide level 1 and the two run fused (msm_planes_level01);
+  // a lone wide leaf level (two-level trees, c = 3: knobs only) takes the step path
+  if (n_wide < 2) n_wide = 0;
+  path[10] = n_wide;
+  proj28_slot* tmp[2] = {nullptr, nullptr};
+  {
+    size_t need[2] = {0, 0};
+    uint32_t kk = 0, flip = 0;
+    while (kk < levels) {
+      const uint32_t m = kk < n_wide ? 1 : (levels - kk < PLANES_STEP_LOG ? levels - kk : PLANES_STEP_LOG);
+      kk += m;
+      if (kk < levels) {
+        const size_t slots = (size_t)(total >> kk) * (kk + 1);
+        if (slots > need[flip]) need[flip] = slots;
       }
       flip ^= 1;
     }
-    if (!table_c)           // W roots of c values each -> W x quads partial Horner values (the host finishes what msm.rs:42-46, 107-115 compute)
-      hipLaunchKernelGGL(msm_planes_window_quads, dim3(W), dim3(64), 0, st, roots, plan.c, quads, window_sum, long_count + 1, offsets + total,
-                         reinterpret_cast<uint32_t*>(window_sum + n_planes));
-  } else {
-#ifdef BP_EXPERIMENT
-    hipLaunchKernelGGL(msm_reduce, dim3(blocks_per_window, Wr), dim3(256), 256 * sizeof(proj28_slot), st, offsets, plan, bucket_sum,
-                       block_out);
-    hipLaunchKernelGGL(msm_window_finish, dim3(Wr), dim3(256), 256 * sizeof(proj28_slot), st, block_out, blocks_per_window, window_sum,
-                       long_count + 1, offsets + total, reinterpret_cast<uint32_t*>(window_sum + n_planes));
-#endif
+    if (need[0]) BP_TRY(ws_get(ctx, "msm.planes_tmp0", need[0] * sizeof(proj28_slot), (void**)&tmp[0]));
+    if (need[1]) BP_TRY(ws_get(ctx, "msm.planes_tmp1", need[1] * sizeof(proj28_slot), (void**)&tmp[1]));
   }
+  const proj28_slot* in = bucket_sum;
+  int flip = 0;
+  while (k < levels) {
+    const bool leaf = k == 0;
+    if (leaf && n_wide) {                 // levels 0 and 1 in one launch, four buckets per lane
+      nodes >>= 2;
+      flip ^= 1;                          // the output takes the buffer level 1 would have taken
+      hipLaunchKernelGGL(msm_planes_level01, dim3((nodes + 255) / 256), dim3(256), 0, st, offsets, in, nodes, tmp[flip]);
+      in = tmp[flip];
+      k = 2;
+    } else if (k < n_wide) {
+      nodes >>= 1;
+      const uint64_t items = (uint64_t)nodes * (k + 1);
+      const dim3 grid((unsigned)((items + 255) / 256));
+      hipLaunchKernelGGL(msm_planes_level, grid, dim3(256), 0, st, offsets, in, k, nodes, tmp[flip]);
+      in = tmp[flip];
+      k += 1;
+    } else {
+      const uint32_t m = levels - k < PLANES_STEP_LOG ? levels - k : PLANES_STEP_LOG;
+      nodes >>= m;
+      const bool last = k + m == levels;
+      proj28_slot* out_nodes = last ? (table_c ? window_sum : roots) : tmp[flip];
+      uint32_t* status_out = last && table_c ? reinterpret_cast<uint32_t*>(window_sum + n_planes) : (uint32_t*)nullptr;
+      const dim3 grid(nodes, k + 1);
+      const size_t lds = ((size_t)2 << m) * sizeof(proj28_slot);
+      if (leaf) hipLaunchKernelGGL(msm_planes_step<true>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
+      else hipLaunchKernelGGL(msm_planes_step<false>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
+      in = out_nodes;
+      k += m;
+    }
+    flip ^= 1;
+  }
+  if (!table_c)           // W roots of c values each -> W x quads partial Horner values (the host finishes what msm.rs:42-46, 107-115 compute)
+    hipLaunchKernelGGL(msm_planes_window_quads, dim3(W), dim3(64), 0, st, roots, plan.c, quads, window_sum, long_count + 1, offsets + total,
+                       reinterpret_cast<uint32_t*>(window_sum + n_planes));
   BP_HIP(ctx, hipGetLastError());
   if (d_blob) {
     MsmBlobHeader hdr;

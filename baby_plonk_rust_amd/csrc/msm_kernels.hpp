@@ -5,13 +5,14 @@
 // Any bucket method yields the same group element, and parity is defined on its affine encoding
 // (SURVEY.md section 8a), so the device algorithm is chosen for the hardware:
 //
-//   1. msm_digits       scalars (Montgomery Fr, coalesced 32-B loads) -> canonical integer ->
-//                       W signed c-bit digits (bias trick, no carry chain), written window-major.
-//   2. msm_count        per (window, slice) workgroup: LDS histogram of the 2^(c-1) buckets of one
-//                       window (c = 16 -> 128 KiB, which is why LDS size picks c), flushed to HBM.
-//   3. scan_*           exclusive scan of all W * 2^(c-1) bucket sizes -> bucket offsets (3 launches).
-//   4. msm_scatter      same LDS histogram; one global atomic per (workgroup, bucket) reserves a range,
-//                       LDS atomics rank inside it; point indices land bucket-sorted (counting sort).
+//   4. bucket sort      scalars (Montgomery Fr) -> canonical integer -> W signed digits (bias trick, no carry chain; radix R
+//                       with tables, msm_digits.hpp) -> the entries (point or table index | sign) in bucket order + the buckets'
+//                       offsets.  No digit array is ever written: the digits are cut in registers wherever they are needed.
+//      4d (default)     msm_part_count, msm_part_scatter: entries partitioned by the high bits of their bucket id, then
+//                       msm_radix_final: one workgroup sorts a final run in an LDS histogram of at most 2^15 buckets
+//                       (128 KiB, which is why LDS size bounds c without tables); msm_radix_long_*: the runs too long for that.
+//      4c (beyond ~5 * 10^7 entries)   the same first level, a second one over records (msm_radix_count, scan_*,
+//                       msm_radix_scatter), the same final pass.
 //   5. msm_accumulate   the hot loop.  The bucket-sorted index list is cut into equal chunks, one per
 //                       lane, regardless of bucket boundaries: every lane performs the same number of
 //                       complete mixed additions (gathered 112-B points of the unsaturated SRS copy, 14 x 28-bit
@@ -19,11 +20,11 @@
 //                       so wave utilisation does not depend on the scalar distribution.  Runs that
 //                       cover a whole bucket are stored as the bucket sum; runs cut by a chunk edge go
 //                       to a per-lane partial slot.
-//   6. msm_fixup        buckets that straddle chunks: add their partials.
-//   7. msm_reduce       sum_b b * S_b per window by segmented running sums + LDS tree; with fixed-base tables
-//      msm_planes_*     (one bucket set for all windows) as bit planes T_j = sum of the buckets with bit j set:
-//                       a binary tree in LDS, two additions per bucket, dependent chain of log2(B) additions.
-//   host epilogue       Horner over the W window sums / the bit planes (c doublings per window, msm.rs:107-115)
+//   6. msm_fixup*       buckets that straddle chunks: add their partials.
+//   7. msm_planes_*     sum_b (b + 1) S_b of a bucket set as bit planes T_j = sum of the buckets with bit j set: a binary tree,
+//                       two additions per bucket, dependent chain of log2(B) additions -- over the one bucket set of fixed-base
+//                       tables (J sets for a batch) or the forest of the W per-window sets (then msm_planes_window_quads).
+//   host epilogue       Horner over the bit planes / the windows' quads (c doublings per window, msm.rs:107-115)
 //                       + one affine normalisation.
 //
 // Group law: complete RCB formulas (g1.hpp) -- branch-free, so P+P / P+(-P) / identity need no
@@ -49,8 +50,6 @@ struct MsmPlan {
   uint32_t lanes;      // 0: the chunk is fixed (BP_MSM_CHUNK).  Else the lanes of msm_accumulate = ceil(W n / chunk): the kernels cut
                        // the sorted list into ceil(M / lanes) entries per lane from the ACTUAL entry count M (zero digits are
                        // not entries: small or sparse scalars keep every lane busy with short chains instead of a few lanes with long ones)
-  uint32_t slices;     // workgroups per window in count/scatter
-  uint32_t seg;        // buckets per lane in msm_reduce
   uint32_t bias[9];    // sum_{w < W-1} 2^(c-1) * 2^(c*w)   (the top window is unsigned)
   // Two bucket layouts share every kernel.  Per-window buckets (any point set): window w owns buckets
   // [w B, (w+1) B) and an entry is the point index i.  Fixed-base tables (bp_srs_precompute): the SRS carries
@@ -88,74 +87,11 @@ struct MsmPlan {
 constexpr uint32_t MSM_MAX_BATCH = 4;
 struct MsmScalars { const fr_t* p[MSM_MAX_BATCH]; };
 
-// ---------------------------------------------------------------- 1. digits
-#ifdef BP_EXPERIMENT      // one-histogram counting sort (BP_MSM_SORT=0): digit array pass
-// fmt 0: 32-byte little-endian canonical (Scalar::to_bytes), 1: Montgomery limbs (Scalar::to_array)
-__global__ void __launch_bounds__(256) msm_digits(const fr_t* __restrict__ scalars, int fmt, MsmPlan plan,
-                                                   int16_t* __restrict__ digits, uint32_t* __restrict__ status) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= plan.n) return;
-  fr_t k = scalars[i];
-  if (fmt == 1) {
-    Fr::from_mont(k, k);                           // msm.rs:126: scalar.to_bytes() = canonical integer
-  } else {
-    fr_t t;                                        // Scalar::from_bytes rejects values >= q (scalar.rs:264-288)
-    if (!big_sub(t, k, Fr::modulus())) atomicOr(status, 1u);
-  }
-  uint32_t kp[10];
-  uint64_t carry = 0;
-#pragma unroll
-  for (int j = 0; j < 9; j++) {
-    carry += (uint64_t)(j < 8 ? k.l[j] : 0u) + plan.bias[j];
-    kp[j] = (uint32_t)carry;
-    carry >>= 32;
-  }
-  kp[9] = 0;
-  const uint32_t c = plan.c, mask = (1u << c) - 1u, half = 1u << (c - 1);
-  for (uint32_t w = 0; w < plan.W; w++) {
-    uint32_t o = c * w, word = o >> 5, sh = o & 31;
-    uint64_t two = (uint64_t)kp[word] | ((uint64_t)kp[word + 1] << 32);
-    // windows below the top one are signed (bias already added); the top window keeps its small unsigned value
-    int32_t d = (int32_t)((uint32_t)(two >> sh) & mask) - (w + 1 < plan.W ? (int32_t)half : 0);
-    digits[(size_t)w * plan.n + i] = (int16_t)d;
-  }
-}
-
-#endif  // BP_EXPERIMENT
 // bucket index inside a window for a non-zero digit: |d| - 1 in [0, 2^(c-1))
 __device__ __forceinline__ uint32_t digit_bucket(int32_t d) { return (uint32_t)(d < 0 ? -d : d) - 1u; }
 
-// ---------------------------------------------------------------- 2. count
-extern __shared__ uint32_t msm_lds_hist[];
+extern __shared__ uint32_t msm_lds_hist[];        // one run's bucket histogram (msm_radix_final, msm_radix_long_*)
 
-__device__ __forceinline__ void slice_range(const MsmPlan& plan, uint32_t slice, uint32_t& lo, uint32_t& hi) {
-  uint32_t per = (plan.n + plan.slices - 1) / plan.slices;
-  lo = slice * per;
-  hi = lo + per < plan.n ? lo + per : plan.n;
-  if (lo > plan.n) lo = plan.n;
-}
-
-#ifdef BP_EXPERIMENT      // one-histogram counting sort: count pass
-__global__ void __launch_bounds__(1024) msm_count(const int16_t* __restrict__ digits, MsmPlan plan,
-                                                  uint32_t* __restrict__ counts) {
-  const uint32_t w = blockIdx.y, B = plan.B;
-  for (uint32_t b = threadIdx.x; b < B; b += blockDim.x) msm_lds_hist[b] = 0;
-  __syncthreads();
-  uint32_t lo, hi;
-  slice_range(plan, blockIdx.x, lo, hi);
-  const int16_t* dw = digits + (size_t)w * plan.n;
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    int32_t d = dw[i];
-    if (d != 0) atomicAdd(&msm_lds_hist[digit_bucket(d)], 1u);
-  }
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < B; b += blockDim.x) {
-    uint32_t v = msm_lds_hist[b];
-    if (v) atomicAdd(&counts[(size_t)w * plan.wbuckets + b], v);
-  }
-}
-
-#endif  // BP_EXPERIMENT
 // ---------------------------------------------------------------- 3. scan (three small launches)
 // offsets[0..total] = exclusive prefix sums of counts[0..total); cursors = copy of offsets[0..total).
 // Tile = 4096 counts per workgroup (256 lanes x 16).  scan_tile_sums -> scan_block_sums -> scan_apply.
@@ -232,37 +168,6 @@ __global__ void __launch_bounds__(256) scan_apply(const uint32_t* __restrict__ c
   }
 }
 
-#ifdef BP_EXPERIMENT      // one-histogram counting sort: scatter pass
-// ---------------------------------------------------------------- 4. scatter (counting sort)
-__global__ void __launch_bounds__(1024) msm_scatter(const int16_t* __restrict__ digits, MsmPlan plan,
-                                                    uint32_t* __restrict__ cursors, uint32_t* __restrict__ sorted) {
-  const uint32_t w = blockIdx.y, B = plan.B;
-  for (uint32_t b = threadIdx.x; b < B; b += blockDim.x) msm_lds_hist[b] = 0;
-  __syncthreads();
-  uint32_t lo, hi;
-  slice_range(plan, blockIdx.x, lo, hi);
-  const int16_t* dw = digits + (size_t)w * plan.n;
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    int32_t d = dw[i];
-    if (d != 0) atomicAdd(&msm_lds_hist[digit_bucket(d)], 1u);
-  }
-  __syncthreads();
-  // reserve this workgroup's range in every bucket it touches; LDS now holds the range start
-  for (uint32_t b = threadIdx.x; b < B; b += blockDim.x) {
-    uint32_t v = msm_lds_hist[b];
-    if (v) msm_lds_hist[b] = atomicAdd(&cursors[(size_t)w * plan.wbuckets + b], v);
-  }
-  __syncthreads();
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    int32_t d = dw[i];
-    if (d != 0) {
-      uint32_t pos = atomicAdd(&msm_lds_hist[digit_bucket(d)], 1u);
-      sorted[pos] = (i + w * plan.wpoints) | (d < 0 ? 0x80000000u : 0u);
-    }
-  }
-}
-
-#endif  // BP_EXPERIMENT
 // exclusive scan of one value per lane over a 1024-lane workgroup (16 waves); lds16: 16 words
 __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t* lds16) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -280,12 +185,13 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32
   return base + incl - v;
 }
 // ---------------------------------------------------------------- 4c. partitioned bucket sort (MSD radix, coalesced)
-// msm_scatter pays for every entry with an isolated 4-byte store: a workgroup's ~32 Ki entries land in ~32 Ki different bucket
-// regions, the lines leave L2 partially written, and HBM sees ~10x the payload (PMC WRITE_SIZE, round 1).  Here the entries are
-// first PARTITIONED by the high bits of their bucket id into runs small enough (~12 Ki entries, ~48 KiB of output) that the
-// final counting sort of a run -- one workgroup, all of the run's buckets -- scatters inside a region L2 holds and merges:
-//   msm_digit_records   scalar -> W (key, value) records: key = bucket id (0xffffffff for a zero digit), value = entry | sign
-//   msm_radix_count     per run and per slice of 8 192 records: LDS histogram of the next `bits` key bits -> sub-run sizes
+// A counting sort over all buckets at once (round 1) pays for every entry with an isolated 4-byte store: a workgroup's ~32 Ki entries
+// land in ~32 Ki different bucket regions, the lines leave L2 partially written, and HBM sees ~10x the payload (PMC WRITE_SIZE).
+// Here the entries are first PARTITIONED by the high bits of their bucket id into runs small enough (~12 Ki entries, ~48 KiB of
+// output) that the final counting sort of a run -- one workgroup, all of the run's buckets -- scatters inside a region L2 holds and
+// merges.  Records are (key, value) pairs: key = bucket id (0xffffffff for an empty NAF slot), value = entry | sign.
+//   level 1             from the scalars (msm_part_count + msm_part_scatter, section 4d), or msm_naf_records for NAF digits
+//   msm_radix_count    per run and per slice of 8 192 records: LDS histogram of the next `bits` key bits -> sub-run sizes
 //   (scan_*)            exclusive scan of the sub-run sizes = sub-run offsets (sub-runs of run j are consecutive inside run j)
 //   msm_radix_scatter   same slices: rank in LDS, stage the slice sorted by digit, write every sub-run's share lane-adjacent
 //   msm_radix_final     one workgroup per final run: histogram of its 2^rbits buckets, prefix = the buckets' offsets (written
@@ -293,39 +199,6 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32
 // One or two partition levels of <= 8 bits each; the record arrays ping-pong.
 constexpr uint32_t RADIX_SLICE = 8192, RADIX_PER_LANE = RADIX_SLICE / 1024, RADIX_MAX_DIGITS = 256, RADIX_EMPTY = 0xffffffffu;
 
-#ifdef BP_EXPERIMENT      // records-first level 1 of the two-level sort (BP_MSM_SORT=1; NAF digits): the shipped build takes level 1 from the scalars
-__global__ void __launch_bounds__(256) msm_digit_records(const fr_t* __restrict__ scalars, int fmt, MsmPlan plan, uint32_t* __restrict__ keys,
-                                                          uint32_t* __restrict__ vals, uint32_t* __restrict__ status) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= plan.n) return;
-  fr_t k = scalars[i];
-  if (fmt == 1) {
-    Fr::from_mont(k, k);
-  } else {
-    fr_t t;
-    if (!big_sub(t, k, Fr::modulus())) atomicOr(status, 1u);
-  }
-  uint32_t kp[10];
-  uint64_t carry = 0;
-#pragma unroll
-  for (int j = 0; j < 9; j++) {
-    carry += (uint64_t)(j < 8 ? k.l[j] : 0u) + plan.bias[j];
-    kp[j] = (uint32_t)carry;
-    carry >>= 32;
-  }
-  kp[9] = 0;
-  const uint32_t c = plan.c, mask = (1u << c) - 1u, half = 1u << (c - 1);
-  for (uint32_t w = 0; w < plan.W; w++) {
-    uint32_t o = c * w, word = o >> 5, sh = o & 31;
-    uint64_t two = (uint64_t)kp[word] | ((uint64_t)kp[word + 1] << 32);
-    int32_t d = (int32_t)((uint32_t)(two >> sh) & mask) - (w + 1 < plan.W ? (int32_t)half : 0);
-    const size_t at = (size_t)w * plan.n + i;
-    keys[at] = d == 0 ? RADIX_EMPTY : w * plan.wbuckets + digit_bucket(d);
-    vals[at] = (i + w * plan.wpoints) | (d < 0 ? 0x80000000u : 0u);
-  }
-}
-
-#endif  // BP_EXPERIMENT
 #ifdef BP_EXPERIMENT      // every-position tables with NAF digits (bp_srs_precompute(h, 256 + w))
 // Width-w NAF records of every scalar (plan.naf = w): slot s of scalar i at [s * n + i].  With E = (k >> pos) + carry:
 // E even -> next position; E odd -> e = E mod 2^w, digit d = e (carry 0) or e - 2^w (carry 1) when e >= 2^(w-1), pos += w.
@@ -608,8 +481,8 @@ __global__ void __launch_bounds__(1024) msm_radix_long_scatter(RunRecords<PACKED
 }
 
 // ---------------------------------------------------------------- 4d. partition sort (one level, digits recomputed, no digit or record pass)
-// The default bucket sort.  The histogram sort of section 4 pays one global atomic per (workgroup, bucket) it touches -- ~10^7 of
-// them at 2^20 points, twice -- and isolated 4-byte stores; the two-level sort of 4c moves 8-byte records three times.  Here:
+// The default bucket sort.  A counting sort over all buckets at once (round 1) pays one global atomic per (workgroup, bucket) it touches
+// -- ~10^7 of them at 2^20 points, twice -- and isolated 4-byte stores; the two-level sort of 4c moves 8-byte records twice.  Here:
 //   msm_part_count     a workgroup per slice of scalars: Montgomery -> canonical -> digits in registers, LDS histogram of the
 //                      entries' PARTITIONS (the high pb bits of the bucket id, <= 2^12), one global atomic per (workgroup,
 //                      partition); the workgroup that finishes last (a ticket) scans the 2^pb sizes = the final runs' offsets
@@ -1038,7 +911,7 @@ __device__ __forceinline__ uint32_t bucket_of(const uint32_t* __restrict__ offse
   return lo;
 }
 
-template <int WAVES>      // waves per SIMD the register allocator must leave room for
+template <int WAVES>      // waves per SIMD the register allocator must leave room for: instantiated at 2 only (three and four both spill)
 __global__ void __launch_bounds__(256, WAVES)
 msm_accumulate(const g1_affine28* __restrict__ points, const uint32_t* __restrict__ sorted,
                const uint32_t* __restrict__ offsets, MsmPlan plan, proj28_slot* __restrict__ bucket_sum,
@@ -1123,7 +996,7 @@ __global__ void __launch_bounds__(256) msm_write_blob(const proj28_slot* __restr
   if (threadIdx.x == 0) {
     if (hdr.n_planes) {
       const uint32_t* tail = reinterpret_cast<const uint32_t*>(window_sum + hdr.n_planes);
-      hdr.status = tail[0];             // scalar >= q seen by msm_digits
+      hdr.status = tail[0];             // scalar >= q seen by the sort's first pass
       hdr.entries = tail[1];
     }
     *reinterpret_cast<MsmBlobHeader*>(blob) = hdr;
@@ -1350,54 +1223,6 @@ __device__ __forceinline__ g1_proj28 block_tree_sum28(g1_proj28 v, uint32_t live
   return load_proj28(&tree[0]);
 }
 
-#ifdef BP_EXPERIMENT     // rounds 1-4: the table-free reduction (BP_MSM_REDUCE=1); the shipped library runs the bit-plane tree over every bucket set
-// ---------------------------------------------------------------- 7a. reduce, per-window buckets: T_w = sum_b (b+1) * S_{w,b}
-// Segmented running sums: grid (blocks_per_window, W), 256 lanes; a lane handles `seg` consecutive buckets, then
-// scales its share by its first bucket index and the block tree-sums in LDS.  With W * B buckets there is enough
-// parallel work to hide the ~50-operation chain per lane.  out[w * gridDim.x + blockIdx.x] = this block's share.
-__global__ void __launch_bounds__(256, 2)
-msm_reduce(const uint32_t* __restrict__ offsets, MsmPlan plan, const proj28_slot* __restrict__ bucket_sum,
-           proj28_slot* __restrict__ block_out) {
-  const uint32_t w = blockIdx.y, B = plan.B, seg = plan.seg;
-  const uint32_t first = (blockIdx.x * blockDim.x + threadIdx.x) * seg;      // first bucket (0-based) of this lane
-  g1_proj28 acc = g1_identity28(), wsum = g1_identity28();
-  if (first < B) {
-    const uint32_t last = first + seg < B ? first + seg : B;
-    for (uint32_t b = last; b-- > first;) {
-      const size_t g = (size_t)w * B + b;
-      if (offsets[g + 1] != offsets[g]) {
-        g1_proj28 s = load_proj28(&bucket_sum[g]);
-        g1_add28(acc, acc, s);
-      }
-      g1_add28(wsum, wsum, acc);                  // after the loop: sum_b (b - first + 1) * S_b
-    }
-    if (first != 0) {                             // + first * acc
-      g1_proj28 scaled;
-      g1_mul_small28(scaled, acc, first, 32 - __clz(first));
-      g1_add28(wsum, wsum, scaled);
-    }
-  }
-  g1_proj28 tot = block_tree_sum28(wsum, blockDim.x);
-  if (threadIdx.x == 0) store_proj28(&block_out[(size_t)w * gridDim.x + blockIdx.x], tot);
-}
-
-// window_sum[w] = sum of the block shares of window w: one workgroup per window, LDS tree over <= 256 shares
-// (the last kernel of an MSM also moves the scalar-status word behind the sums, so that one copy brings everything to the host)
-__global__ void __launch_bounds__(256, 2) msm_window_finish(const proj28_slot* __restrict__ block_out, uint32_t blocks_per_window,
-                                                             proj28_slot* __restrict__ window_sum, const uint32_t* __restrict__ status_in,
-                                                             const uint32_t* __restrict__ entries_in, uint32_t* __restrict__ status_out) {
-  const uint32_t w = blockIdx.x;
-  if (w == 0 && threadIdx.x == 0) { status_out[0] = *status_in; status_out[1] = *entries_in; }    // [1]: non-zero digits = bucket additions done
-  g1_proj28 v = g1_identity28();
-  for (uint32_t j = threadIdx.x; j < blocks_per_window; j += blockDim.x) {       // > 256 shares: fold first
-    g1_proj28 q = load_proj28(&block_out[(size_t)w * blocks_per_window + j]);
-    g1_add28(v, v, q);
-  }
-  g1_proj28 tot = block_tree_sum28(v, blocks_per_window < blockDim.x ? blocks_per_window : blockDim.x);
-  if (threadIdx.x == 0) store_proj28(&window_sum[w], tot);
-}
-#endif
-
 // ---------------------------------------------------------------- 7b. reduce, fixed-base tables (one bucket set):  sum_b (b + 1) S_b  by bit planes
 //   sum_b (b + 1) S_b = A + sum_j 2^j T_j,    A = sum_b S_b,   T_j = sum of the buckets whose index b has bit j set.
 // A binary tree over the bucket index yields A and every T_j with two additions per bucket and a dependent chain
@@ -1437,25 +1262,16 @@ __device__ __forceinline__ proj28_slot* planes_tree(proj28_slot* cur, proj28_slo
 
 // One level of the tree through HBM, one addition per lane ("wide" levels: at least a wave round of additions, where the chip is
 // throughput bound and the cooperative form's doubled work would be the cost).  in: nodes of 2^k buckets, k + 1 values each
-// (LEAF: k = 0, the bucket sums themselves, empty buckets read as the identity); out: n_out nodes of k + 2 values.
+// (k >= 2: the leaves go through msm_planes_level01 or a step); out: n_out nodes of k + 2 values.
 // Lane (node, v), v <= k, adds value v of the node's two children; the lane of v = 0 also moves A_r into the new plane T_k.
-template <bool LEAF>
 __global__ void __launch_bounds__(256, 2)
 msm_planes_level(const uint32_t* __restrict__ offsets, const proj28_slot* __restrict__ in, uint32_t k, uint32_t n_out,
                  proj28_slot* __restrict__ out) {
   const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t per = k + 1, node = (uint32_t)(item / per), v = (uint32_t)(item - (uint64_t)node * per);
   if (node >= n_out) return;
-  g1_proj28 a, b;
-  if (LEAF) {
-    const size_t g = 2 * (size_t)node;
-    a = offsets[g + 1] != offsets[g] ? load_proj28(&in[g]) : g1_identity28();             // empty bucket: slot never written
-    b = offsets[g + 2] != offsets[g + 1] ? load_proj28(&in[g + 1]) : g1_identity28();
-  } else {
-    const proj28_slot* L = in + (size_t)(2 * (size_t)node) * per;
-    a = load_proj28(&L[v]);
-    b = load_proj28(&L[per + v]);
-  }
+  const proj28_slot* L = in + (size_t)(2 * (size_t)node) * per;
+  g1_proj28 a = load_proj28(&L[v]), b = load_proj28(&L[per + v]);
   proj28_slot* o = out + (size_t)node * (per + 1);
   if (v == 0) store_proj28(&o[per], b);                                                    // T_k = A_r
   if (!(is_blank28(a) && is_blank28(b))) g1_add28(a, a, b);                                // empty regions: whole waves skip

@@ -1,7 +1,7 @@
 """-m gpu, experiment build only (BABY_PLONK_LIBRARY=exp): every build of the MSM pipeline stages gives the same bytes.
 
-The bucket sort has three builds (partition sort with packed or two-word records, two-level radix sort, one-histogram counting
-sort), the fix-up two (a lane pair per bucket, a lane per chunk edge), the bit-plane tree two kinds of level (one addition per
+The bucket sort has two builds (partition sort with packed or two-word records; radix sort over one or two levels, level 1 cut
+from the scalars), the fix-up two (a lane pair per bucket, a lane per chunk edge), the bit-plane tree two kinds of level (one addition per
 lane through HBM, cooperative additions inside a workgroup).  The library picks among them by size; the experiment knobs force
 each one here, at a size where every branch (long final runs, long buckets, queued merges) is reached by skewed scalars.
 Expected values: the closed form sum_i s_i (a + i d) G by independent big-int arithmetic (tests/bigint_model.py); the group
@@ -21,8 +21,8 @@ BUILDS = [
     {"BP_MSM_SORT": "2", "BP_MSM_PACKED": "0"},             # partition sort, two-word records
     {"BP_MSM_SORT": "2", "BP_MSM_PART_SLICE": "64"},        # many small slices: one record per (slice, partition) or none
     {"BP_MSM_SORT": "2", "BP_MSM_RADIX_BITS": "0"},         # a single final run (no partition level), packed
-    {"BP_MSM_SORT": "1"},                                   # two-level radix sort
-    {"BP_MSM_SORT": "0"},                                   # histogram sort (c <= 16; wider windows fall back to the default)
+    {"BP_MSM_SORT": "1"},                                   # radix sort, a single level cut from the scalars
+    {"BP_MSM_SORT": "1", "BP_MSM_RADIX_BITS": "10"},        # radix sort, two levels: the route of more than ~5 * 10^7 entries
     {"BP_MSM_FIXUP": "1"},                                  # fix-up per bucket
     {"BP_MSM_FIXUP": "2"},                                  # fix-up per chunk edge
     {"BP_MSM_PLANES_WIDE_MIN": "256"},                      # tree: every level with >= 256 additions through HBM
@@ -56,12 +56,17 @@ def problem(ctx):
 @pytest.mark.parametrize("build", BUILDS, ids=lambda b: ",".join("%s=%s" % (k[7:], v) for k, v in b.items()))
 def test_builds_agree(ctx, problem, tables, build, monkeypatch):
     h, n, sets, want = problem
+    naf = tables == 256 + 12
+    if naf and "BP_MSM_RADIX_BITS" in build and build.get("BP_MSM_SORT") == "1":
+        pytest.skip("10 partition bits forced onto 2^10 NAF buckets: a corner nobody needs")
     for k, v in build.items():
         monkeypatch.setenv(k, v)
     info = ctx.srs_precompute(h, tables)
     assert info["window_bits"] == (0 if tables == 1 else tables)
     for name, sc in sets.items():
         assert ctx.msm(h, sc) == want[name], (name, tables, build)
+        if build.get("BP_MSM_SORT") == "1" and not naf:
+            assert ctx.msm_path()["sort"] == 1, (name, tables, build)       # no silent fall-back to the partition sort
         st = ctx.msm_stats()
         assert st["tables"] == (tables != 1) and 0 < st["mixed_adds"] <= 64 * n
     # a prefix that ends inside a slice and a shard at an offset, through the same build

@@ -206,8 +206,7 @@ class Context:
 
     def srs_precompute(self, handle, window_bits=0):
         """fixed-base window tables T[w][i] = 2^(c w) P_i for an SRS that serves many MSMs (0 = auto width,
-        SRS_TABLES_OFF drops them; 256 + w = tables of every bit position for width-w NAF digits: experiment build only,
-        the shipped library raises BpError(BP_ERR_INVALID_ARG) for it)"""
+        SRS_TABLES_OFF drops them, else 4..24; anything else raises BpError(BP_ERR_INVALID_ARG))"""
         self.check(self._lib.bp_srs_precompute(self._h, handle, window_bits), "bp_srs_precompute")
         return self.srs_table_info(handle)
 

@@ -462,8 +462,8 @@ static int msm_blob_device(bp_ctx* ctx, uint64_t srs_handle, size_t first, const
   if (wait) return msm_finish(ctx, pend, nullptr);
   // nothing is waited for: the stats of this MSM are read from its events by bp_msm_last_stats once the stream has passed them
   ctx->msm_async_pending = !pend.empty;
-  ctx->msm_c = pend.tables == 2 ? (MSM_NAF_FLAG | (pend.c + 1)) : pend.c;
-  ctx->msm_tables = pend.tables != 0;
+  ctx->msm_c = pend.c;
+  ctx->msm_tables = pend.tables;
   ctx->msm_adds = pend.adds;
   if (pend.empty) ctx->msm_accumulate_ms = ctx->msm_total_ms = 0;
   return BP_OK;

@@ -367,7 +367,7 @@ static int srs_precompute_one(bp_ctx* ctx, SrsEntry* e, uint32_t c) {
 
 // fixed-base tables of width c (as bp_srs_precompute takes it) pay for an MSM of n points once the bucket adds outweigh the
 // fixed 2^c reduction
-static bool srs_width_pays(uint32_t c, size_t n) { return 8 * (uint64_t)n >= (1ull << ((c & MSM_NAF_FLAG) ? (c & 0xffu) - 2 : c)); }
+static bool srs_width_pays(uint32_t c, size_t n) { return 8 * (uint64_t)n >= (1ull << c); }
 bool srs_tables_pay(const SrsEntry& e, size_t n) { return e.d_table && srs_width_pays(e.table_c, n); }
 
 int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
@@ -390,11 +390,8 @@ int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
       c = lg > 8 ? lg - 4 : 4;        // reduction tree has c - 1 levels -- measured optimum 2^10: 6, 2^12: 8
     }
   }
-  const bool naf = (c & MSM_NAF_FLAG) != 0;
-  if (naf && !EXPERIMENT_BUILD)        // every-position tables with NAF digits: measured slower twice, experiment builds only
+  if (c != BP_SRS_TABLES_OFF && (c < 4 || c > 24))
     return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off) or 4..24");
-  if (naf ? ((c & 0xffu) < 6 || (c & 0xffu) > 22 || (c >> 9)) : (c != BP_SRS_TABLES_OFF && (c < 4 || c > 24)))
-    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off), 4..24, or 256 + w (w = 6..22: every-position tables)");
   // Memory budget: the tables (rows x points x 128 B: 25.8 GB per GPU at 2^24 points) must fit beside whatever else lives on the
   // device -- a second prover context, the caller's tensors -- together with the workspaces the first MSM against them allocates.
   // The check comes BEFORE anything is released or allocated, and counts the bytes of the tables this SRS holds now as free (they

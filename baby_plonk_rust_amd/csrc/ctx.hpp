@@ -19,8 +19,7 @@ namespace bp {
 // Experiment knobs.  The shipped library reads NO environment variable: every default is the measured best and nothing in the
 // embedding process's environment can change a kernel shape.  A build with -DBP_EXPERIMENT (`make exp` -> libbp_msm_ntt_exp.so,
 // loaded by the tests under tests/ that are marked `experiment`, and by the A/B tools) reads the BP_* variables of DESIGN.md
-// section 12, compiles the alternative build they select (every-position NAF tables) and
-// honours the test hook BP_FORCE_PEER_COPIES.
+// section 12 and honours the test hook BP_FORCE_PEER_COPIES.
 #ifdef BP_EXPERIMENT
 inline const char* knob(const char* name) { return getenv(name); }
 constexpr bool EXPERIMENT_BUILD = true;
@@ -41,9 +40,6 @@ struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
 };
-
-// SrsEntry::table_c = MSM_NAF_FLAG | w: tables of every bit position (MSM_NAF_ROWS rows) for width-w NAF digits (msm_kernels.hpp MsmPlan::naf)
-constexpr uint32_t MSM_NAF_FLAG = 0x100u, MSM_NAF_ROWS = 256;
 
 struct SrsEntry {
   g1_affine* d_points = nullptr;        // 96 B/point, reference Montgomery limbs (export, generic kernels)
@@ -286,7 +282,7 @@ int pinned_get(bp_ctx* ctx, size_t bytes, void** out);
 constexpr int MSM_SLOTS = 4;
 struct MsmPending {
   bool empty = true, blob = false;
-  uint32_t tables = 0;                  // 0: per-window buckets; 1: fixed-base window tables; 2: every-position tables (odd NAF digits)
+  bool tables = false;                  // fixed-base window tables (false: per-window buckets)
   uint32_t c = 0, Wr = 0, n_planes = 0;
   uint32_t quads = 1;                   // table-free: values per window the device hands over (msm_planes_window_quads); 1: whole window sums
   uint32_t J = 1;                       // scalar vectors in the pipeline (msm_launch_many): msm_finish writes J results

@@ -45,25 +45,6 @@ static void make_plan(MsmPlan& plan, size_t n, uint32_t table_c, size_t table_st
   plan.n = (uint32_t)n;
   plan.J = J;
   plan.nj[0] = (uint32_t)n;
-  if (table_c & MSM_NAF_FLAG) {         // every-position tables: odd NAF digits of width w, 2^(w-2) buckets, one bucket set
-    const uint32_t w = table_c & 0xffu;
-    plan.naf = w;
-    plan.c = w - 1;
-    plan.W = 255 / w + 1;               // digit slots per scalar (most scalars fill 256 / (w + 1) of them)
-    plan.B = 1u << (w - 2);
-    plan.total = J * plan.B;
-    plan.wbuckets = 0;
-    plan.wpoints = (uint32_t)table_stride;
-    plan.parts = plan.B <= (1u << MSM_HIST_LOG) ? 1 : plan.B >> MSM_HIST_LOG;
-    // lanes: one wave round (131 072) for the worst case of every slot filled; the kernels cut the sorted list by the actual
-    // entry count (a uniform scalar fills 256 / (w + 1) + ~0.45 of its slots: 15.49 / 13.91 / 12.71 at w = 16 / 18 / 20)
-    uint32_t chunk = (uint32_t)(((uint64_t)plan.W * n * J + 131071) / 131072);
-    if (chunk < 4) chunk = 4;
-    if (chunk > 1024) chunk = 1024;
-    plan.chunk = knob_u32("BP_MSM_CHUNK", chunk, 1, 1024);
-    plan.lanes = knob_u32("BP_MSM_CHUNK", 0, 1, 1024) ? 0u : (uint32_t)(((uint64_t)plan.W * n * J + plan.chunk - 1) / plan.chunk);
-    return;
-  }
   uint32_t c = n < 32 ? 4 : ilog2_floor(n) - 3;
   if (c < 4) c = 4;
   if (c > MSM_MAX_C) c = MSM_MAX_C;
@@ -158,20 +139,17 @@ int srs_to28_into(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28* d_o
   return BP_OK;
 }
 
-uint32_t msm_table_windows(uint32_t c) {
-  if (c & MSM_NAF_FLAG) return MSM_NAF_ROWS;
+// table[w * n + i] = 2^(c w) P_i; row 0 is the unsaturated SRS copy itself
+uint32_t srs_table_rows(uint32_t c) {
   MsmPlan plan;
   make_plan(plan, 1, c, 1);
   return plan.W;
 }
 
-// table[w * n + i] = 2^(c w) P_i; row 0 is the unsaturated SRS copy itself
-uint32_t srs_table_rows(uint32_t c) { return msm_table_windows(c); }
-
 int srs_tables_run(bp_ctx* ctx, const g1_affine* d_points, const g1_affine28* d_points28, size_t n, uint32_t c, g1_affine28** d_table,
                    uint32_t* windows) {
-  const uint32_t W = msm_table_windows(c);
-  const uint32_t radix = (c & MSM_NAF_FLAG) ? 0u : msm_table_radix(c, W);       // rows R^w P_i where the MSM cuts radix-R digits (MsmPlan::radix)
+  const uint32_t W = srs_table_rows(c);
+  const uint32_t radix = msm_table_radix(c, W);       // rows R^w P_i where the MSM cuts radix-R digits (MsmPlan::radix)
   if ((uint64_t)W * n >= (1ull << 31))
     return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "fixed-base tables: windows * points >= 2^31");
   g1_affine28* t = nullptr;
@@ -179,7 +157,7 @@ int srs_tables_run(bp_ctx* ctx, const g1_affine* d_points, const g1_affine28* d_
   if (n) {
     BP_HIP(ctx, hipMemcpyAsync(t, d_points28, n * sizeof(g1_affine28), hipMemcpyDeviceToDevice, ctx->stream));
     if (radix) hipLaunchKernelGGL(srs_window_tables<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_points28, n, c, W, radix, t);
-    else hipLaunchKernelGGL(srs_window_tables<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_points28, n, (c & MSM_NAF_FLAG) ? 1u : c, W, 0u, t);
+    else hipLaunchKernelGGL(srs_window_tables<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_points28, n, c, W, 0u, t);
   }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = stream_wait(ctx->stream);
@@ -347,7 +325,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   // record form of the partition sort: the packed word holds the bucket's low kb - pb bits, the sign and the entry (point or
   // table index, vb - 1 bits).  Where a few more partitions make the record fit one word (c = 20 at 2^20: 2^12 instead of 2^10)
   // they are taken: half the bytes through the scatter and the final sort (BP_MSM_PACKED=2 keeps the run length instead).
-  const uint64_t idx_max = (uint64_t)(n - 1) + (uint64_t)(plan.naf ? 255u : W - 1) * plan.wpoints;
+  const uint64_t idx_max = (uint64_t)(n - 1) + (uint64_t)(W - 1) * plan.wpoints;
   uint32_t vb = 1;
   while ((idx_max >> (vb - 1)) != 0) vb++;                              // vb - 1 = bits of the largest entry, + 1 for the sign
   const uint32_t packed_env = knob_u32("BP_MSM_PACKED", 1, 0, 2);
@@ -402,7 +380,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
                                                                vb, cap, cur, recs, rvals, roff, offsets, sorted, rlong_n, rlong_list, counts, cursors, run_ticket);
   } else if (sort_mode == 1) {
     const uint32_t lv[2] = {pb <= 8 ? pb : pb - pb / 2, pb <= 8 ? 0 : pb / 2};
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *run_off[3], *cnt, *cur;
+    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *cnt, *cur;
     BP_TRY(ws_get(ctx, "msm.rkeys0", max_entries * 4, (void**)&keys[0]));
     BP_TRY(ws_get(ctx, "msm.rvals0", max_entries * 4, (void**)&vals[0]));
     if (pb) {
@@ -411,68 +389,52 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     }
     uint32_t* roff;
     BP_TRY(ws_get(ctx, "msm.run_off", ((size_t)3 * n_final + 16) * 4, (void**)&roff));
-    run_off[0] = roff;                                   // {0, W n}
-    run_off[1] = roff + 4;                               // after level 1: 2^lv[0] + 1 entries
-    run_off[2] = roff + 8 + n_final;                     // after level 2: n_final + 1 entries
+    uint32_t* const run_off[2] = {roff + 4,                 // after level 1: 2^lv[0] + 1 entries
+                                  roff + 8 + n_final};      // after level 2: n_final + 1 entries
     BP_TRY(ws_get(ctx, "msm.run_cnt", (size_t)n_final * 4, (void**)&cnt));
     BP_TRY(ws_get(ctx, "msm.run_cur", (size_t)n_final * 4, (void**)&cur));
-    const uint32_t whole[2] = {0u, (uint32_t)max_entries};
-    BP_HIP(ctx, hipMemcpyAsync(run_off[0], whole, sizeof whole, hipMemcpyHostToDevice, st));
     uint32_t* rlong_list;
     BP_TRY(ws_get(ctx, "msm.run_long", ((size_t)n_final + 2) * 4, (void**)&rlong_list));
     // Level 1 comes straight from the scalars, as the partition sort does it (msm_part_count + msm_part_scatter with two-word records into
-    // 2^lv[0] runs: no record pass, one array's traffic less -- 2^24 points, tail 5.87 -> 5.32 ms, profiles/r04_sort24_hybrid_ab.txt).  NAF
-    // digits (experiment build) are written as records first (msm_naf_records) and partitioned by msm_radix_count / _scatter at both levels.
-    uint32_t runs = 1, shift = kb, side = 0;
-    int first_level = 0;
-    if (!plan.naf) {
-      const uint32_t pb1 = lv[0], rb1 = kb - pb1;
+    // 2^lv[0] runs: no record pass, one array's traffic less -- 2^24 points, tail 5.87 -> 5.32 ms, profiles/r04_sort24_hybrid_ab.txt).
+    const uint32_t pb1 = lv[0], rb1 = kb - pb1;
+    {
       const uint32_t slice = part_slice(64, 1024, 512, n, (uint64_t)W * 8), slice1 = part_slice(slice, 8192, 256, n, 0);
       const uint32_t cap = slice * W, n_slices = (uint32_t)(((uint64_t)n + slice - 1) / slice);
       const unsigned threads = slice >= 1024 ? 1024u : (slice <= 256 ? 256u : slice);
       const uint32_t n_slices1 = (uint32_t)(((uint64_t)n + slice1 - 1) / slice1);
-      hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb1, rb1, ctl + 4, run_off[1], cur,
+      hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb1, rb1, ctl + 4, run_off[0], cur,
                          long_count + 1);
       const size_t part_lds = (size_t)3 * (1u << pb1) * 4 + (size_t)cap * 8;
       hipLaunchKernelGGL((msm_part_scatter<false, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb1, rb1, 0u, cap, cur, keys[1],
                          vals[1]);
-      runs = 1u << pb1;
-      shift = rb1;
-      side = 1;
-      first_level = 1;
-    } else {
-#ifdef BP_EXPERIMENT
-      hipLaunchKernelGGL(msm_naf_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars_each[0], fmt, plan, keys[0], vals[0], long_count + 1);
-#else
-      return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "NAF tables are an experiment build");      // unreachable: bp_srs_precompute refuses them in this build
-#endif
     }
-    for (int level = first_level; level < 2 && lv[level]; level++) {
-      const uint32_t bits = lv[level], nd = 1u << bits, n_sub = runs * nd;
-      shift -= bits;
+    uint32_t runs = 1u << pb1, side = 1;
+    if (lv[1]) {                    // the second level: msm_radix_count / _scatter cut each run of level 1 by the next lv[1] bits
+      const uint32_t bits = lv[1], nd = 1u << bits, n_sub = runs * nd, shift = rb1 - bits;
       uint64_t per_run = max_entries / runs;
       uint32_t gx = (uint32_t)((per_run + RADIX_SLICE - 1) / RADIX_SLICE) + (runs > 1 ? 1 : 0);
       if (gx > 4096) gx = 4096;
       const uint32_t t = (n_sub + SCAN_TILE - 1) / SCAN_TILE;
       BP_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)n_sub * 4, st));
-      hipLaunchKernelGGL(msm_radix_count, dim3(gx, runs), dim3(1024), 0, st, keys[side], run_off[level], shift, bits, cnt);
+      hipLaunchKernelGGL(msm_radix_count, dim3(gx, runs), dim3(1024), 0, st, keys[side], run_off[0], shift, bits, cnt);
       hipLaunchKernelGGL(scan_tile_sums, dim3(t), dim3(256), 0, st, cnt, n_sub, tile_sums);
-      hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(256), 0, st, tile_sums, t, run_off[level + 1] + n_sub);
-      hipLaunchKernelGGL(scan_apply, dim3(t), dim3(256), 0, st, cnt, n_sub, tile_sums, run_off[level + 1], cur);
-      hipLaunchKernelGGL(msm_radix_scatter, dim3(gx, runs), dim3(1024), RADIX_SLICE * 9, st, keys[side], vals[side], run_off[level], shift, bits,
+      hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(256), 0, st, tile_sums, t, run_off[1] + n_sub);
+      hipLaunchKernelGGL(scan_apply, dim3(t), dim3(256), 0, st, cnt, n_sub, tile_sums, run_off[1], cur);
+      hipLaunchKernelGGL(msm_radix_scatter, dim3(gx, runs), dim3(1024), RADIX_SLICE * 9, st, keys[side], vals[side], run_off[0], shift, bits,
                          cur, keys[side ^ 1], vals[side ^ 1]);
       side ^= 1;
       runs = n_sub;
     }
-    const uint32_t level_count = (lv[0] ? 1 : 0) + (lv[1] ? 1 : 0);
+    uint32_t* const final_off = run_off[lv[1] ? 1 : 0];
     const RunRecords<false> rr{keys[side], vals[side], (1u << rbits) - 1u, 0u};
-    hipLaunchKernelGGL(msm_radix_final<false>, dim3(runs < 4096 ? runs : 4096), dim3(1024), rhist, st, rr, run_off[level_count], runs, rbits, total, offsets,
+    hipLaunchKernelGGL(msm_radix_final<false>, dim3(runs < 4096 ? runs : 4096), dim3(1024), rhist, st, rr, final_off, runs, rbits, total, offsets,
                        sorted, rlong_n, rlong_list, counts);
     if (runs > 1) {                 // long runs (none for uniformly random scalars beyond the top window's): slice-parallel
       const dim3 lgrid(256, runs < 16 ? runs : 16);
-      hipLaunchKernelGGL(msm_radix_long_count<false>, lgrid, dim3(1024), rhist, st, rr, run_off[level_count], runs, rbits, total, rlong_n, rlong_list, counts,
+      hipLaunchKernelGGL(msm_radix_long_count<false>, lgrid, dim3(1024), rhist, st, rr, final_off, runs, rbits, total, rlong_n, rlong_list, counts,
                          offsets, cursors, run_ticket);
-      hipLaunchKernelGGL(msm_radix_long_scatter<false>, lgrid, dim3(1024), rhist, st, rr, run_off[level_count], rbits, rlong_n, rlong_list, cursors, sorted);
+      hipLaunchKernelGGL(msm_radix_long_scatter<false>, lgrid, dim3(1024), rhist, st, rr, final_off, rbits, rlong_n, rlong_list, cursors, sorted);
     }
   }
   BP_HIP(ctx, hipEventRecord(ctx->ev[1], st));
@@ -569,7 +531,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     hdr.c = plan.c;
     hdr.Wr = table_c ? 1 : Wr;
     hdr.n_planes = n_planes;
-    hdr.tables = plan.naf ? 2u : (table_c != 0 ? 1u : 0u);
+    hdr.tables = table_c != 0;
     hdr.quads = table_c ? 0u : quads;
     hipLaunchKernelGGL(msm_write_blob, dim3(1), dim3(256), 0, st, window_sum, hdr, (uint8_t*)d_blob);
     BP_HIP(ctx, hipGetLastError());
@@ -578,7 +540,7 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   }
   BP_HIP(ctx, hipEventRecord(ctx->ev[3], st));
   out->empty = false;
-  out->tables = plan.naf ? 2u : (table_c != 0 ? 1u : 0u);
+  out->tables = table_c != 0;
   out->c = plan.c;
   out->Wr = table_c ? 1 : Wr;
   out->n_planes = n_planes;
@@ -613,9 +575,8 @@ static void host_quad_horner(g1_proj& out, const g1_proj* quads, uint32_t W, uin
 }
 
 // planes[w * c + 0] = A_w, planes[w * c + 1 + j] = T_{w,j} (j < c - 1):
-//   out = sum_w 2^(c w) (A_w + sum_j 2^j T_{w,j}),  one pass from the top bit position down (bucket b holds digit b + 1);
-//   odd_digits (NAF tables, one window): bucket b holds digit 2b + 1, out = A + 2 sum_j 2^j T_j
-static void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, uint32_t c, bool odd_digits = false) {
+//   out = sum_w 2^(c w) (A_w + sum_j 2^j T_{w,j}),  one pass from the top bit position down (bucket b holds digit b + 1)
+static void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, uint32_t c) {
   g1_proj acc = g1_identity();
   for (uint32_t w = W; w-- > 0;) {
     const g1_proj* p = planes + (size_t)w * c;
@@ -623,7 +584,6 @@ static void host_plane_horner(g1_proj& out, const g1_proj* planes, uint32_t W, u
       g1_double(acc, acc);
       if (j + 1 < c) g1_add(acc, acc, p[1 + j]);           // bit position c - 1 of the window carries no plane
     }
-    if (odd_digits) g1_double(acc, acc);
     g1_add(acc, acc, p[0]);
   }
   out = acc;
@@ -643,8 +603,8 @@ int msm_finish(bp_ctx* ctx, const MsmPending& pend, g1_proj* host_out) {
   BP_HIP(ctx, stream_wait(ctx->stream));
   BP_HIP(ctx, hipEventElapsedTime(&ctx->msm_accumulate_ms, ctx->ev[1], ctx->ev[2]));
   BP_HIP(ctx, hipEventElapsedTime(&ctx->msm_total_ms, ctx->ev[0], ctx->ev[3]));
-  ctx->msm_c = pend.tables == 2 ? (MSM_NAF_FLAG | (pend.c + 1)) : pend.c;       // as given to bp_srs_precompute
-  ctx->msm_tables = pend.tables != 0;
+  ctx->msm_c = pend.c;
+  ctx->msm_tables = pend.tables;
   ctx->msm_adds = pend.adds;
   if (pend.blob) {                      // the result stayed in HBM (bp_msm_g1_blob_device); its status word travels in the record
     if (host_out) *host_out = g1_identity();
@@ -659,7 +619,7 @@ int msm_finish(bp_ctx* ctx, const MsmPending& pend, g1_proj* host_out) {
   for (uint32_t w = 0; w < n_planes; w++) windows[w] = slot_to_proj(&h_windows[w]);
   if (pend.tables) {
     for (uint32_t j = 0; j < pend.J; j++)              // a batch: c values per vector, one Horner pass each
-      host_plane_horner(host_out[j], windows.data() + (size_t)j * pend.c, pend.Wr, pend.c, pend.tables == 2);
+      host_plane_horner(host_out[j], windows.data() + (size_t)j * pend.c, pend.Wr, pend.c);
   } else {
     host_quad_horner(*host_out, windows.data(), pend.Wr, pend.c, pend.quads);
   }
@@ -679,8 +639,9 @@ int msm_blobs_combine(const uint8_t* blobs, size_t n_blobs, g1_proj* out) {
     if (h.err != 0) return h.err < 0 && h.err >= BP_ERR_COMM ? h.err : BP_ERR_INVALID_ARG;       // a rank's poisoned record: its code for every rank (msm_blob_poisoned names the rank)
     // the Horner passes below index the slots by (Wr, c): a record whose header does not describe its own slot count (another
     // library version on a peer rank, a truncated gather) is rejected here instead of being read past its end
+    if (h.tables > 1) return BP_ERR_INVALID_ARG;          // 0 or 1; any other value is another library's record (older experiment builds wrote 2)
     if (h.n_planes != 0) {
-      const bool width_ok = h.tables == 2 ? (h.c >= 5 && h.c <= 21) : (h.tables <= 1 && h.c >= 2 && h.c <= (uint32_t)MSM_MAX_TABLE_C);
+      const bool width_ok = h.c >= 2 && h.c <= (uint32_t)MSM_MAX_TABLE_C;
       const uint32_t per = h.tables ? h.c : (h.quads ? h.quads : 1u);
       if (!width_ok || h.Wr < 1 || per > 8 * 4 || h.n_planes != h.Wr * per) return BP_ERR_INVALID_ARG;
     }
@@ -704,7 +665,7 @@ int msm_blobs_combine(const uint8_t* blobs, size_t n_blobs, g1_proj* out) {
       for (uint32_t w = 0; w < h.n_planes; w++) g1_add(sum[w], sum[w], slot_to_proj(&sk[w]));
     }
     g1_proj part;
-    if (h.tables) host_plane_horner(part, sum.data(), h.Wr, h.c, h.tables == 2);
+    if (h.tables) host_plane_horner(part, sum.data(), h.Wr, h.c);
     else host_quad_horner(part, sum.data(), h.Wr, h.c, h.quads ? h.quads : 1u);
     g1_add(total, total, part);
   }

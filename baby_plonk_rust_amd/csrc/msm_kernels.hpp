@@ -61,11 +61,6 @@ struct MsmPlan {
   // Windows wider than 16 bits (fixed-base tables only): one window's 2^(c-1) buckets no longer fit one LDS histogram
   // (parts > 1); those MSMs take the partitioned (radix) bucket sort, section 4c.
   uint32_t parts;      // 1, or B >> 15
-  // Fixed-base tables of EVERY bit position (T[p][i] = 2^p P_i, 256 rows: the 288 GB of HBM pay for it up to ~2^21 points) carry
-  // the scalar's width-`naf` non-adjacent form: odd digits |d| < 2^(naf-1) at arbitrary positions, at most one per `naf`
-  // positions -- 256 / (naf + 1) bucket additions per scalar on average instead of 256 / c, with only 2^(naf-2) buckets
-  // (bucket (|d| - 1) / 2).  Then c = naf - 1 (so that B = 2^(c-1) as everywhere), W = digit slots per scalar.
-  uint32_t naf;        // 0, or the NAF width
   // Several scalar vectors against ONE table set in one pipeline (the commitments of a prover round, prover.rs:249-251,
   // 483-485, 640-641): vector j owns the buckets [j B, (j + 1) B), so the sort, the accumulation, the fix-up and the tree run
   // once over J bucket sets and deliver J results.  n is then the longest vector; scalar (j, i) is element j * n + i of the
@@ -189,72 +184,16 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32
 // land in ~32 Ki different bucket regions, the lines leave L2 partially written, and HBM sees ~10x the payload (PMC WRITE_SIZE).
 // Here the entries are first PARTITIONED by the high bits of their bucket id into runs small enough (~12 Ki entries, ~48 KiB of
 // output) that the final counting sort of a run -- one workgroup, all of the run's buckets -- scatters inside a region L2 holds and
-// merges.  Records are (key, value) pairs: key = bucket id (0xffffffff for an empty NAF slot), value = entry | sign.
-//   level 1             from the scalars (msm_part_count + msm_part_scatter, section 4d), or msm_naf_records for NAF digits
+// merges.  Records are (key, value) pairs: key = bucket id, value = entry | sign; only non-zero digits have one.
+//   level 1             from the scalars (msm_part_count + msm_part_scatter with two-word records, section 4d)
 //   msm_radix_count    per run and per slice of 8 192 records: LDS histogram of the next `bits` key bits -> sub-run sizes
 //   (scan_*)            exclusive scan of the sub-run sizes = sub-run offsets (sub-runs of run j are consecutive inside run j)
 //   msm_radix_scatter   same slices: rank in LDS, stage the slice sorted by digit, write every sub-run's share lane-adjacent
 //   msm_radix_final     one workgroup per final run: histogram of its 2^rbits buckets, prefix = the buckets' offsets (written
 //                       to `offsets` directly: no global count / scan over buckets), then the entries in bucket order
 // One or two partition levels of <= 8 bits each; the record arrays ping-pong.
-constexpr uint32_t RADIX_SLICE = 8192, RADIX_PER_LANE = RADIX_SLICE / 1024, RADIX_MAX_DIGITS = 256, RADIX_EMPTY = 0xffffffffu;
+constexpr uint32_t RADIX_SLICE = 8192, RADIX_PER_LANE = RADIX_SLICE / 1024, RADIX_MAX_DIGITS = 256;
 
-#ifdef BP_EXPERIMENT      // every-position tables with NAF digits (bp_srs_precompute(h, 256 + w))
-// Width-w NAF records of every scalar (plan.naf = w): slot s of scalar i at [s * n + i].  With E = (k >> pos) + carry:
-// E even -> next position; E odd -> e = E mod 2^w, digit d = e (carry 0) or e - 2^w (carry 1) when e >= 2^(w-1), pos += w.
-// k < 2^255, so every digit sits at a position <= 255 and there are at most 255 / w + 1 of them (= plan.W slots).
-__global__ void __launch_bounds__(256) msm_naf_records(const fr_t* __restrict__ scalars, int fmt, MsmPlan plan, uint32_t* __restrict__ keys,
-                                                        uint32_t* __restrict__ vals, uint32_t* __restrict__ status) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= plan.n) return;
-  fr_t k = scalars[i];
-  if (fmt == 1) {
-    Fr::from_mont(k, k);
-  } else {
-    fr_t t;
-    if (!big_sub(t, k, Fr::modulus())) atomicOr(status, 1u);
-  }
-  uint32_t kw[10];
-#pragma unroll
-  for (int j = 0; j < 8; j++) kw[j] = k.l[j];
-  kw[8] = 0;
-  kw[9] = 0;
-  const uint32_t w = plan.naf, mask = (1u << w) - 1u, half = 1u << (w - 1);
-  uint32_t pos = 0, carry = 0, slot = 0;
-  while (pos < 256 && slot < plan.W) {
-    // next position >= pos whose bit differs from the carry (there E is odd); none below 256: the rest of E is zero
-    const uint32_t flip = carry ? 0xffffffffu : 0u;
-    uint32_t word = pos >> 5, x = ((kw[word] ^ flip) >> (pos & 31));
-    uint32_t p = pos;
-    if (x) {
-      p += __ffs(x) - 1;
-    } else {
-      p = (word + 1) << 5;
-      for (word++; word < 8 && (kw[word] ^ flip) == 0; word++) p += 32;
-      if (word >= 8) {
-        if (!carry) break;                    // carry == 0: k has no bits left.  carry == 1 reaches here only past bit 255 (bit 255 of k is 0)
-        p = 256;
-      } else {
-        p += __ffs(kw[word] ^ flip) - 1;
-      }
-    }
-    if (p >= 256) break;
-    const uint32_t wd = p >> 5, sh = p & 31;
-    const uint64_t two = (uint64_t)kw[wd] | ((uint64_t)kw[wd + 1] << 32);
-    const uint32_t e = ((uint32_t)(two >> sh) & mask) + carry;        // odd, < 2^w
-    const bool neg = e >= half;
-    const uint32_t mag = neg ? (1u << w) - e : e;                     // |d|, odd, < 2^(w-1)
-    carry = neg ? 1u : 0u;
-    const size_t at = (size_t)slot * plan.n + i;
-    keys[at] = (mag - 1) >> 1;
-    vals[at] = (i + p * plan.wpoints) | (neg ? 0x80000000u : 0u);
-    slot++;
-    pos = p + w;
-  }
-  for (; slot < plan.W; slot++) keys[(size_t)slot * plan.n + i] = RADIX_EMPTY;
-}
-
-#endif  // BP_EXPERIMENT
 // run r = records [run_off[r], run_off[r + 1]); the workgroups blockIdx.x, blockIdx.x + gridDim.x, ... take its slices
 __global__ void __launch_bounds__(1024) msm_radix_count(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ run_off, uint32_t shift,
                                                         uint32_t bits, uint32_t* __restrict__ cnt) {
@@ -267,7 +206,7 @@ __global__ void __launch_bounds__(1024) msm_radix_count(const uint32_t* __restri
     const uint32_t end = base + RADIX_SLICE < hi ? (uint32_t)base + RADIX_SLICE : hi;
     for (uint32_t j = (uint32_t)base + threadIdx.x; j < end; j += blockDim.x) {
       const uint32_t key = keys[j];
-      if (key != RADIX_EMPTY) atomicAdd(&h[(key >> shift) & (nd - 1)], 1u);
+      atomicAdd(&h[(key >> shift) & (nd - 1)], 1u);
     }
   }
   __syncthreads();
@@ -280,6 +219,7 @@ __global__ void __launch_bounds__(1024) msm_radix_scatter(const uint32_t* __rest
                                                           uint32_t* __restrict__ cursor, uint32_t* __restrict__ keys_out,
                                                           uint32_t* __restrict__ vals_out) {
   __shared__ uint32_t h[RADIX_MAX_DIGITS], lbase[RADIX_MAX_DIGITS], gbase[RADIX_MAX_DIGITS], scan16[16];
+  constexpr uint32_t RADIX_EMPTY = 0xffffffffu;       // a lane past the end of the run (no bucket id reaches it: total <= 2^25)
   uint32_t* st_key = msm_radix_lds;
   uint32_t* st_val = st_key + RADIX_SLICE;
   uint8_t* st_d = reinterpret_cast<uint8_t*>(st_val + RADIX_SLICE);
@@ -344,7 +284,6 @@ struct RunRecords {
 // One workgroup per final run (grid-stride).  The run's keys share their high bits; its 2^rbits buckets are
 // [run << rbits, (run + 1) << rbits).  Writes offsets[bucket] for those (only below `total`) and the run's entries in bucket
 // order; the scattered 4-byte stores stay inside the run's own ~48 KiB of `sorted`, which L2 merges into whole lines.
-// keys may still hold RADIX_EMPTY records when no partition level ran (single run, two-array form): they are skipped.
 // Runs longer than RADIX_LONG_RUN records (skewed scalars; the narrow top window, whose few buckets collect n entries) are
 // not sorted by one workgroup: they are queued in long_list and handled slice-parallel by the msm_radix_long_* kernels
 // (zero_counts != null: the queueing workgroup clears the run's bucket counters for them).
@@ -370,11 +309,10 @@ __global__ void __launch_bounds__(1024) msm_radix_final(RunRecords<PACKED> recs,
     __syncthreads();
     for (uint32_t j = lo + threadIdx.x; j < hi; j += blockDim.x) {
       const uint32_t key = recs.load(j);
-      if (PACKED || key != RADIX_EMPTY) atomicAdd(&msm_lds_hist[recs.low(key)], 1u);
+      atomicAdd(&msm_lds_hist[recs.low(key)], 1u);
     }
     __syncthreads();
-    // exclusive prefix over the nb bucket sizes, 1024 at a time; the prefix replaces the size in LDS (it becomes the cursor).
-    // Without a partition level the run still holds its zero-digit records: output positions start at `lo` and close up.
+    // exclusive prefix over the nb bucket sizes, 1024 at a time; the prefix replaces the size in LDS (it becomes the cursor)
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (uint32_t b0 = 0; b0 < nb; b0 += blockDim.x) {
@@ -392,7 +330,7 @@ __global__ void __launch_bounds__(1024) msm_radix_final(RunRecords<PACKED> recs,
     if (run == n_runs - 1 && threadIdx.x == 0) offsets[total] = lo + carry;
     for (uint32_t j = lo + threadIdx.x; j < hi; j += blockDim.x) {
       const uint32_t key = recs.load(j);
-      if (PACKED || key != RADIX_EMPTY) sorted[lo + atomicAdd(&msm_lds_hist[recs.low(key)], 1u)] = recs.val(j, key);
+      sorted[lo + atomicAdd(&msm_lds_hist[recs.low(key)], 1u)] = recs.val(j, key);
     }
     __syncthreads();
   }
@@ -493,7 +431,7 @@ __global__ void __launch_bounds__(1024) msm_radix_long_scatter(RunRecords<PACKED
 // No digit array, no record arrays before the final runs, no scan launches.
 constexpr uint32_t PART_MAX_BITS = 12, PART_MAX = 1u << PART_MAX_BITS;
 
-// every (bucket id, entry | sign << 31) of scalar i, in window (or NAF slot) order.  status != null: canonical-bytes inputs are
+// every (bucket id, entry | sign << 31) of scalar i with a non-zero digit, in window order.  status != null: canonical-bytes inputs are
 // range-checked (Scalar::from_bytes rejects values >= q, scalar.rs:264-288)
 // the scalar as the canonical integer the digits are cut from
 __device__ __forceinline__ void msm_scalar_canon(fr_t& k, int fmt, uint32_t* __restrict__ status) {
@@ -506,43 +444,6 @@ __device__ __forceinline__ void msm_scalar_canon(fr_t& k, int fmt, uint32_t* __r
 }
 template <class F>
 __device__ __forceinline__ void msm_canon_entries(const fr_t& k, uint32_t i, uint32_t bucket_base, const MsmPlan& plan, F&& emit) {
-  if (plan.naf) {                                  // as msm_naf_records
-    uint32_t kw[10];
-#pragma unroll
-    for (int j = 0; j < 8; j++) kw[j] = k.l[j];
-    kw[8] = 0;
-    kw[9] = 0;
-    const uint32_t w = plan.naf, mask = (1u << w) - 1u, half = 1u << (w - 1);
-    uint32_t pos = 0, carry = 0, slot = 0;
-    while (pos < 256 && slot < plan.W) {
-      const uint32_t flip = carry ? 0xffffffffu : 0u;
-      uint32_t word = pos >> 5, x = ((kw[word] ^ flip) >> (pos & 31));
-      uint32_t p = pos;
-      if (x) {
-        p += __ffs(x) - 1;
-      } else {
-        p = (word + 1) << 5;
-        for (word++; word < 8 && (kw[word] ^ flip) == 0; word++) p += 32;
-        if (word >= 8) {
-          if (!carry) break;
-          p = 256;
-        } else {
-          p += __ffs(kw[word] ^ flip) - 1;
-        }
-      }
-      if (p >= 256) break;
-      const uint32_t wd = p >> 5, sh = p & 31;
-      const uint64_t two = (uint64_t)kw[wd] | ((uint64_t)kw[wd + 1] << 32);
-      const uint32_t e = ((uint32_t)(two >> sh) & mask) + carry;
-      const bool neg = e >= half;
-      const uint32_t mag = neg ? (1u << w) - e : e;
-      carry = neg ? 1u : 0u;
-      emit(bucket_base + ((mag - 1) >> 1), (i + p * plan.wpoints) | (neg ? 0x80000000u : 0u));
-      slot++;
-      pos = p + w;
-    }
-    return;
-  }
   if (plan.radix) {                                // digits in radix R (MsmPlan::radix, msm_digits.hpp), top window first
     msm_radix_digits(k.l, plan.radix, plan.radix_m, plan.bias, plan.W, [&](uint32_t w, int32_t d) {
       if (d != 0) emit(bucket_base + digit_bucket(d), (i + w * plan.wpoints) | (d < 0 ? 0x80000000u : 0u));

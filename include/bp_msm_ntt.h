@@ -157,10 +157,8 @@ int  bp_srs_free(bp_ctx* ctx, uint64_t srs_handle);
  * for lack of memory -- a width that does not fit beside what else lives on the device falls back to wider windows (fewer rows; only
  * widths an MSM over this SRS would use, 8 * srs_len >= 2^width) and then to no tables at all (bp_srs_table_info reports what was
  * built; results are the same bytes either way); an explicit width that does not fit returns BP_ERR_TOO_LARGE with the sizes in
- * bp_last_error() before anything is released or allocated: the SRS keeps the tables it had.
- * window_bits = 256 + w (w = 6..22: tables of EVERY bit position, T[p][i] = 2^p * P_i for p < 256, used with the scalars' width-w
- * non-adjacent form) exists ONLY in the experiment build libbp_msm_ntt_exp.so (measured slower twice, docs/EXPERIMENTS.md C); the
- * shipped library rejects it with BP_ERR_INVALID_ARG. */
+ * bp_last_error() before anything is released or allocated: the SRS keeps the tables it had.  Any other window_bits is
+ * BP_ERR_INVALID_ARG, and the SRS keeps its tables likewise. */
 #define BP_SRS_TABLES_OFF 1u
 int  bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits);
 /* window_bits / windows / bytes of the tables of an SRS (all 0 without tables). */

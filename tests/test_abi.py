@@ -193,6 +193,14 @@ def test_blob_combine_host_side():
     assert e.value.code == -4
     with pytest.raises(bp.BpError):
         bp.combine_blobs(bytes(_lib.MSM_BLOB_BYTES))
+    # `tables` is 0 or 1: a record that says 2 (as an older experiment library wrote them), however well formed otherwise, is refused
+    ks = [rnd.randrange(1, M.Q) for _ in range(c)]
+    for good, bad in ((True, 2), (False, 2), (True, 3)):
+        rec = _blob(c, [_slot(M.ec_mul(k)) for k in ks], good)
+        assert len(bp.combine_blobs(rec)) == 96
+        with pytest.raises(bp.BpError) as e:
+            bp.combine_blobs(rec[:16] + int(bad).to_bytes(4, "little") + rec[20:])
+        assert e.value.code == -1, bad
 
 
 def test_window_scalars_are_what_the_reference_walks():

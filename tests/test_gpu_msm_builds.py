@@ -52,20 +52,17 @@ def problem(ctx):
     ctx.srs_free(h)
 
 
-@pytest.mark.parametrize("tables", [1, 13, 16, 18, 20, 256 + 12], ids=lambda t: "tables_%d" % t)
+@pytest.mark.parametrize("tables", [1, 13, 16, 18, 20], ids=lambda t: "tables_%d" % t)
 @pytest.mark.parametrize("build", BUILDS, ids=lambda b: ",".join("%s=%s" % (k[7:], v) for k, v in b.items()))
 def test_builds_agree(ctx, problem, tables, build, monkeypatch):
     h, n, sets, want = problem
-    naf = tables == 256 + 12
-    if naf and "BP_MSM_RADIX_BITS" in build and build.get("BP_MSM_SORT") == "1":
-        pytest.skip("10 partition bits forced onto 2^10 NAF buckets: a corner nobody needs")
     for k, v in build.items():
         monkeypatch.setenv(k, v)
     info = ctx.srs_precompute(h, tables)
     assert info["window_bits"] == (0 if tables == 1 else tables)
     for name, sc in sets.items():
         assert ctx.msm(h, sc) == want[name], (name, tables, build)
-        if build.get("BP_MSM_SORT") == "1" and not naf:
+        if build.get("BP_MSM_SORT") == "1":
             assert ctx.msm_path()["sort"] == 1, (name, tables, build)       # no silent fall-back to the partition sort
         st = ctx.msm_stats()
         assert st["tables"] == (tables != 1) and 0 < st["mixed_adds"] <= 64 * n
@@ -79,8 +76,9 @@ def test_builds_agree(ctx, problem, tables, build, monkeypatch):
 def test_environment_knobs_out_of_range_are_ignored(ctx, problem, monkeypatch):
     """a stray variable in the embedding process must not change kernel shapes or divide by zero"""
     h, n, sets, want = problem
-    for k, v in {"BP_MSM_CHUNK": "0", "BP_MSM_SLICES": "0", "BP_MSM_SEG": "0", "BP_MSM_C": "99", "BP_MSM_SORT": "7", "BP_MSM_PART_SLICE": "3",
-                 "BP_MSM_RADIX_BITS": "x", "BP_MSM_PLANES_WIDE_MIN": "0", "BP_MSM_FIXUP": "-1"}.items():
+    for k, v in {"BP_MSM_CHUNK": "0", "BP_MSM_PACKED": "9", "BP_MSM_PART_WIDE8": "x", "BP_MSM_RADIX_FROM": "0", "BP_MSM_COUNT_SLICE": "1",
+                 "BP_MSM_FINAL_THREADS": "7", "BP_MSM_C": "99", "BP_MSM_SORT": "7", "BP_MSM_PART_SLICE": "3", "BP_MSM_RADIX_BITS": "x",
+                 "BP_MSM_PLANES_WIDE_MIN": "0", "BP_MSM_FIXUP": "-1"}.items():
         monkeypatch.setenv(k, v)
     assert ctx.msm(h, sets["random"]) == want["random"]
     ctx.srs_precompute(h, 0)

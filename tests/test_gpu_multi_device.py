@@ -376,7 +376,7 @@ def test_projective_seam_in_one_call(monkeypatch):
     m = n - 12345
     assert ctx.msm_projective144(img, sc[:m]) == ctx.msm(h2, sc[:m])
     assert ctx.msm_projective144(img[: 144 * m], sc) == ctx.msm(h2, sc[:m])
-    # canonical bytes; a scalar >= q in the third piece of four is refused, and the next call is unaffected
+    # canonical bytes; a scalar >= q in the third piece of four is refused, and the next call works as before
     le = np.frombuffer(b"".join(s.to_bytes(32, "little") for s in ints), dtype=np.uint8).reshape(-1, 32).copy()
     assert ctx.msm_projective144(img, le, fmt=bp.FR_BYTES_LE) == want
     le[(5 * n) // 8] = 0xFF

@@ -46,6 +46,7 @@ ERRORS = {
 FR_BYTES_LE, FR_MONT = 0, 1
 MSM_BLOB_BYTES = 22592          # BP_MSM_BLOB_BYTES
 SRS_CHECK_SUBGROUP = 1          # BP_SRS_CHECK_SUBGROUP (bp_srs_load_compressed48 checks)
+SRS_CHECK_GENERATOR = 2         # BP_SRS_CHECK_GENERATOR (bp_srs_check_powers checks)
 COMM_ID_BYTES = 128             # BP_COMM_ID_BYTES (RCCL's ncclUniqueId)
 BASIS_LAGRANGE, BASIS_MONOMIAL = 0, 1
 
@@ -77,6 +78,13 @@ SIGNATURES = {
     "bp_srs_table_info": (_int, [_vp, _u64, _pp(_u32), _pp(_u32), _pp(_u64)]),
     "bp_srs_lagrange": (_int, [_vp, _u64, _u32, _pp(_u64)]),
     "bp_srs_basis": (_int, [_vp, _u64, _pp(_int), _pp(_u32)]),
+    "bp_srs_powers_reduce": (_int, [_vp, _u64, _sz, _sz, _vp, _int, _vp]),
+    "bp_srs_check_powers": (_int, [_vp, _u64, _vp, _vp, _int, _u32, _pp(_sz)]),
+    "bp_srs_check_last_stats": (_int, [_vp, _pp(_u32), _pp(_u32), _pp(C.c_float)]),
+    "bp_srs_adopt_lagrange": (_int, [_vp, _u64, _u64, _u32, _vp, _int, _pp(_u64), _pp(_sz)]),
+    "bp_srs_scale": (_int, [_vp, _u64, _vp, _sz, _int, _int, _pp(_u64), _pp(_sz)]),
+    "bp_srs_scale_last_stats": (_int, [_vp, _vp]),
+    "bp_g2_mul": (_int, [_vp, _vp, _vp]),
     "bp_msm_last_used_tables": (_int, [_vp]),
     "bp_g1_bytes96_to_compressed48": (_int, [_vp, _vp]),
     "bp_circuit_load": (_int, [_vp, _u32, _vp, _int, _int, _pp(_u64)]),

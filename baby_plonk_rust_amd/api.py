@@ -8,6 +8,7 @@ own tests; where the reference panics (assert!/unwrap) these raise BpError/Asser
   Setup::generate_srs(powers, tau)   setup.rs:12-31   Setup.generate_srs(powers, tau)
   Setup::commit(&poly)               setup.rs:32-37   Setup.commit(poly)
   (no counterpart: KZG open / check)                  Setup.open(polys, z, nu) / Setup.verify_openings(openings)
+  (no counterpart: ceremony files)                    Setup.check_powers() / from_lagrange_points() / contribute(s) / verify_contribution()
   BucketMSM::bucket_msm(p, s, b, c)  msm.rs:76-118    BucketMSM.bucket_msm(points, scalars, b, c)
   ntt_381 / i_ntt_381                utils.rs:63,106  ntt_381(values) / i_ntt_381(values)
   root_of_unity / roots_of_unity     utils.rs:39-52   root_of_unity(n) / roots_of_unity(n)
@@ -58,6 +59,22 @@ def _fr_array(a):
         a = a.reshape(-1, 4)
     assert a.ndim == 2 and a.shape[1] == 4, a.shape
     return a
+
+
+_SIZE_MAX = C.c_size_t(-1).value
+
+
+def _scalar32(v):
+    """an integer as the 32 little-endian bytes of BP_FR_BYTES_LE, NOT reduced: the library refuses a value >= q"""
+    if not 0 <= int(v) < 1 << 256:
+        raise BpError(-4, "scalar", "outside 0 .. 2^256")
+    return np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8).copy()
+
+
+def _draw_rho():
+    """128 random bits with the top bit set: the weight of a random linear combination, drawn once the data is in hand"""
+    import secrets
+    return secrets.randbits(128) | 1 << 127
 
 
 class Context:
@@ -497,6 +514,73 @@ class Context:
         self.check(self._lib.bp_kzg_last_stats(self._h, ms), "bp_kzg_last_stats")
         return dict(zip(("values_quotient_ms", "commit_ms", "reduce_ms"), [float(v) for v in ms]))
 
+    # ---- the structure of an SRS (capi_srs_check.hip) ----
+    def srs_powers_reduce(self, handle, rho, first=0, n_pairs=None):
+        """bp_srs_powers_reduce: (A96, B96) = (sum_i rho^i P_{first+i}, sum_i rho^i P_{first+i+1}) over n_pairs pairs (default: all
+        from `first`); every pair is P_{i+1} = tau P_i exactly when pairing(A, x_2) == pairing(B, G2 generator).  rho: an integer
+        the caller drew after the points were fixed, 128 bits of entropy or more"""
+        n_pairs = self.srs_len(handle) - first - 1 if n_pairs is None else n_pairs
+        r, out = _scalar32(rho), np.zeros(192, dtype=np.uint8)
+        self.check(self._lib.bp_srs_powers_reduce(self._h, handle, first, n_pairs, r.ctypes.data, FR_BYTES_LE, out.ctypes.data), "bp_srs_powers_reduce")
+        return out[:96].tobytes(), out[96:].tobytes()
+
+    def srs_check_powers(self, handle, x_2, rho=None, generator=True):
+        """bp_srs_check_powers: are the points the powers of the tau of x_2 (and, with generator=True, is P_0 the G1 generator)?
+        None, or the lowest bad index: 0 for the generator, else the lowest i with P_i != tau P_{i-1} (1 for a wrong x_2).
+        rho=None draws 128 bits here.  A rejected x_2 raises BpError"""
+        x2 = np.frombuffer(bytes(x_2), dtype=np.uint8).copy()
+        if len(x2) != 192:
+            raise BpError(-6, "bp_srs_check_powers", "x_2: 192 bytes expected")
+        r, bad = _scalar32(_draw_rho() if rho is None else rho), C.c_size_t()
+        rc = self._lib.bp_srs_check_powers(self._h, handle, x2.ctypes.data, r.ctypes.data, FR_BYTES_LE, _lib.SRS_CHECK_GENERATOR if generator else 0,
+                                           C.byref(bad))
+        if rc == -3 and bad.value != _SIZE_MAX:
+            return bad.value
+        self.check(rc, "bp_srs_check_powers")
+        return None
+
+    def srs_check_stats(self):
+        """reduces, host pairings and wall milliseconds of the last srs_check_powers / srs_adopt_lagrange on this context"""
+        a, b, ms = C.c_uint32(), C.c_uint32(), C.c_float()
+        self.check(self._lib.bp_srs_check_last_stats(self._h, C.byref(a), C.byref(b), C.byref(ms)), "bp_srs_check_last_stats")
+        return {"reduces": a.value, "pairings": b.value, "ms": ms.value}
+
+    def srs_adopt_lagrange(self, points, powers, log_n, rho=None):
+        """bp_srs_adopt_lagrange: `points` (a loaded handle of 2^log_n points) checked against the first 2^log_n points of the
+        powers-of-tau handle `powers` -- two MSMs and a transform, no pairing -- and returned as a NEW handle tagged Lagrange.
+        Points that are not the Lagrange points raise BpError(BP_ERR_BAD_POINT) with the lowest wrong index in `index`"""
+        r, h, bad = _scalar32(_draw_rho() if rho is None else rho), C.c_uint64(), C.c_size_t()
+        rc = self._lib.bp_srs_adopt_lagrange(self._h, points, powers, log_n, r.ctypes.data, FR_BYTES_LE, C.byref(h), C.byref(bad))
+        try:
+            self.check(rc, "bp_srs_adopt_lagrange")
+        except BpError as e:
+            e.index = bad.value if rc == -3 and bad.value != _SIZE_MAX else None
+            raise
+        return h.value
+
+    def srs_scale(self, handle, scalars=None, fmt=FR_MONT, device_ptr=None, n=None):
+        """bp_srs_scale: a new SRS handle with points k_i P_i (same basis), one scalar per point: a host array ([n, 4] Montgomery
+        limbs, or [n, 32] canonical bytes with fmt=FR_BYTES_LE) or (device_ptr, n).  The source is subgroup-tested first: a point
+        outside raises BpError(BP_ERR_BAD_POINT) with its index in `index`"""
+        h, bad = C.c_uint64(), C.c_size_t()
+        if device_ptr is not None:
+            rc = self._lib.bp_srs_scale(self._h, handle, device_ptr, n, fmt, 1, C.byref(h), C.byref(bad))
+        else:
+            k = _fr_array(scalars) if fmt == FR_MONT else np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+            rc = self._lib.bp_srs_scale(self._h, handle, k.ctypes.data if len(k) else None, len(k), fmt, 0, C.byref(h), C.byref(bad))
+        try:
+            self.check(rc, "bp_srs_scale")
+        except BpError as e:
+            e.index = bad.value if rc == -3 and bad.value != _SIZE_MAX else None
+            raise
+        return h.value
+
+    def srs_scale_stats(self):
+        """HIP-event milliseconds of the last srs_scale on this context: subgroup test, multiplications, normalisation"""
+        ms = (C.c_float * 3)()
+        self.check(self._lib.bp_srs_scale_last_stats(self._h, ms), "bp_srs_scale_last_stats")
+        return dict(zip(("subgroup_ms", "scale_ms", "normalise_ms"), [float(v) for v in ms]))
+
     def set_stream(self, stream_ptr):
         self.check(self._lib.bp_set_stream(self._h, stream_ptr), "bp_set_stream")
 
@@ -555,6 +639,18 @@ def g2_mul_generator(k_int):
     rc = _lib.load().bp_g2_mul_generator(k.ctypes.data, out.ctypes.data)
     if rc != 0:
         raise BpError(rc, "bp_g2_mul_generator")
+    return bytes(out)
+
+
+def g2_mul(q192, k_int):
+    """host-side: k * Q in G2 (bp_g2_mul), 192 bytes in and out; x_2 of a ceremony contribution is g2_mul(x_2, s)"""
+    q = np.frombuffer(bytes(q192), dtype=np.uint8).copy()
+    if len(q) != 192:
+        raise BpError(-6, "bp_g2_mul", "192 bytes expected")
+    k, out = _scalar32(k_int), np.zeros(192, dtype=np.uint8)
+    rc = _lib.load().bp_g2_mul(q.ctypes.data, k.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise BpError(rc, "bp_g2_mul")
     return bytes(out)
 
 
@@ -940,6 +1036,50 @@ class Setup:
         if group_order < 1 or group_order & (group_order - 1):
             raise BpError(-2, "Setup.lagrange", "group_order %d is not a power of two" % group_order)
         return Setup(self.ctx.srs_lagrange(self.handle, group_order.bit_length() - 1), self.ctx, tables, self.x_2)
+
+    def check_powers(self, rho=None, generator=True):
+        """are the points G, tau G, tau^2 G, ... for the tau of x_2?  (bp_srs_check_powers: one random linear combination, two
+        MSMs, one host pairing check; a failure is located by bisection.)  None, or the lowest bad index -- 0: P_0 is not the
+        generator (generator=True), i >= 1: P_i != tau P_{i-1}.  rho=None draws 128 bits with the top bit set."""
+        if self.x_2 is None:
+            raise BpError(-1, "Setup.check_powers", "the setup has no x_2 (pass x_2= to Setup.from_points / from_compressed)")
+        return self.ctx.srs_check_powers(self.handle, self.x_2, rho, generator)
+
+    @staticmethod
+    def from_lagrange_points(points, powers_setup, rho=None, tables=True, compressed=False):
+        """a Lagrange-basis Setup from SHIPPED Lagrange points (96-byte records, or 48-byte ones with compressed=True; a power of
+        two of them), adopted only after they were checked against powers_setup's powers (bp_srs_adopt_lagrange: no pairing).
+        Same context and x_2 as powers_setup.  Wrong points raise BpError(BP_ERR_BAD_POINT) with the lowest wrong index in `index`."""
+        ctx = powers_setup.ctx
+        n = len(bytes(points)) // (48 if compressed else 96)
+        if n < 1 or n & (n - 1):
+            raise BpError(-2, "Setup.from_lagrange_points", "%d points: not a power of two" % n)
+        loaded = ctx.srs_load_compressed48(points) if compressed else ctx.srs_load(points)
+        try:
+            h = ctx.srs_adopt_lagrange(loaded, powers_setup.handle, n.bit_length() - 1, rho)
+        finally:
+            ctx.srs_free(loaded)
+        return Setup(h, ctx, tables, powers_setup.x_2)
+
+    def contribute(self, s_int, tables=True):
+        """one contribution to the ceremony: a new Setup with points s^i P_i and x_2' = s x_2 (bp_srs_scale, one multiplication
+        per GPU lane; the scalars s^i are made on the device).  The secret s is the caller's to forget."""
+        import torch
+        s_int, c, n = int(s_int) % Q, self.ctx, self.ctx.srs_len(self.handle)
+        ones = DevicePolynomial(np.tile(scalar_from_int(1), (n, 1)), BASIS_MONOMIAL, c)
+        pows = ones.scale_powers(scalar_from_int(s_int))
+        torch.cuda.current_stream().synchronize()
+        h = c.srs_scale(self.handle, device_ptr=pows._ptr(), n=n)
+        return Setup(h, c, tables, None if self.x_2 is None else g2_mul(self.x_2, s_int))
+
+    def verify_contribution(self, previous, s_2):
+        """is this Setup `previous` after ONE contribution whose secret s the contributor published as s_2 = s G2?  The lengths
+        are equal, this Setup is a clean powers-of-tau SRS (check_powers), and pairing(P'_1, G2) == pairing(P_1, s_2)."""
+        n = self.ctx.srs_len(self.handle)
+        if n != previous.ctx.srs_len(previous.handle) or n < 2 or self.check_powers() is not None:
+            return False
+        p1, q1 = previous.ctx.srs_export(previous.handle, 1, 1), self.ctx.srs_export(self.handle, 1, 1)
+        return pairing_check([(p1, q1)], s_2, host=True)[0]
 
     def commit(self, polynomial):
         """setup.rs:32-37: asserts the Monomial basis, then bucket_msm over the whole SRS (a Setup made by lagrange(): asserts the

@@ -44,6 +44,10 @@ std::vector<bp_ctx*> shards_of(bp_ctx* ctx);
 int ctx_create(bp_ctx** out, int device_id);
 // capi_srs.hip
 int srs_find(bp_ctx* ctx, uint64_t handle, bp::SrsEntry** out);
+// A new entry of ctx (one device) over the resident points d: the 28-bit copy is made, the stream waited for.  Takes ownership of d
+// (freed on failure); the entry covers global points [first, first + n) of an SRS of n_global points, Monomial until the caller says otherwise.
+int srs_register(bp_ctx* ctx, bp::g1_affine* d, size_t n, size_t first, size_t n_global, uint64_t* handle);
+int srs_free_one(bp_ctx* ctx, uint64_t handle);            // one member's entry and everything it holds
 // One shard of an SRS: the member that holds it, the member's entry and handle, and the part [lo, hi) of the range asked for
 // that lies on it, in global point indices (lo >= hi: none of it does).
 struct SrsShard {

@@ -17,7 +17,7 @@
 using namespace bp;
 
 // takes ownership of d (freed on failure); the entry covers global points [first, first + n) of an SRS of n_global points
-static int srs_register(bp_ctx* ctx, g1_affine* d, size_t n, size_t first, size_t n_global, uint64_t* handle) {
+int srs_register(bp_ctx* ctx, g1_affine* d, size_t n, size_t first, size_t n_global, uint64_t* handle) {
   SrsEntry e;
   e.d_points = d;
   e.n = n;
@@ -65,7 +65,7 @@ int srs_shards_checked(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n,
   return BP_OK;
 }
 
-static int srs_free_one(bp_ctx* ctx, uint64_t handle) {
+int srs_free_one(bp_ctx* ctx, uint64_t handle) {
   SrsEntry* e;
   BP_TRY(srs_find(ctx, handle, &e));
   DeviceGuard guard(ctx->device);

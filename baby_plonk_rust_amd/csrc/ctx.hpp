@@ -139,6 +139,11 @@ struct bp_ctx {
   // bp_kzg_open(_device): values + quotient | commit; bp_kzg_verify_reduce: the whole reduce; kzg_roots_*: the domain whose roots
   // the workspace "kzg.roots" holds
   float kzg_ms[3] = {0, 0, 0};
+  // bp_srs_check_powers / bp_srs_adopt_lagrange: reduces (adopt: comparisons of two MSMs) and host pairings of the last call and its
+  // host wall time; bp_srs_scale: subgroup test | srs_scale | normalisation of the last call (HIP events; a group: the sum over its shards)
+  uint32_t srs_check_reduces = 0, srs_check_pairings = 0;
+  float srs_check_ms = 0;
+  float srs_scale_ms[3] = {0, 0, 0};
   const void* kzg_roots_ptr = nullptr;
   uint32_t kzg_roots_log_n = 0;
   std::vector<uint8_t> verify_vk_seen;               // the last verifier key it saw (768 bytes) and one byte: all eight commitments in the subgroup?
@@ -269,8 +274,8 @@ struct StreamDrain {
 int ws_get(bp_ctx* ctx, const char* name, size_t bytes, void** out);
 // the context's HIP events `name`, at least `count` of them, created on first use with `flags` and kept until bp_destroy; *out is
 // valid until the next ev_get of the same name (a larger count may move the set).  Every event an entry point records to time its
-// stages or to order the context's stream against the side stream comes from here: "verify", "verify.seg", "pairing", "kzg", "check"
-// and "srs.g1_ntt" (timing enabled), "seam" and "side" (hipEventDisableTiming).  Not from here, because they live and die with
+// stages or to order the context's stream against the side stream comes from here: "verify", "verify.seg", "pairing", "kzg", "check",
+// "srs.g1_ntt" and "srs.scale" (timing enabled), "seam" and "side" (hipEventDisableTiming).  Not from here, because they live and die with
 // something else: ctx->ev (made by ctx_create, read by the MSM / NTT hot path and the *_async pending flags), comm_ev (the communicator, capi_comm.hip) and CosetShare::done (the circuit).
 int ev_get(bp_ctx* ctx, const char* name, size_t count, unsigned flags, hipEvent_t** out);
 int pinned_get(bp_ctx* ctx, size_t bytes, void** out);
@@ -346,6 +351,8 @@ int srs_subgroup_run(bp_ctx* ctx, const g1_affine* d_pts, size_t n, uint64_t* ba
 int srs_encode48_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, uint8_t* d_bytes);
 int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affine* d_out);
 int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t first, size_t n, g1_affine* d_out);
+// d_out[i] = d_scalars[i] * d_pts[i] (srs_scale: Montgomery scalars, subgroup points or the identity), projective; enqueued, not waited for
+int srs_scale_run(bp_ctx* ctx, const g1_affine* d_pts, const fr_t* d_scalars, size_t n, g1_proj* d_out);
 // the inverse transform over G1 of d_in[0 .. 2^log_n) (g1_ntt.hpp) -> affine points; waits for the stream
 int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_out);
 // kzg.hip: the values y_j = f_j(z) (host_y, count of them) and the quotient (sum_j nu^j f_j - sum_j nu^j y_j) / (x - z) of count

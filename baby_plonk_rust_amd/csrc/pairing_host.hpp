@@ -112,5 +112,16 @@ inline int host_g2_mul_generator(const uint8_t k32[32], uint8_t out192[192]) {
   g2_encode192(out192, g2_to_affine(g2_mul(g2_generator(), k, 8)));
   return BP_OK;
 }
+// k * Q for any point Q of the curve (curve-checked here, not subgroup-checked) and a canonical little-endian k < q: x_2 of a
+// ceremony contribution is s * x_2.  An identity Q or k = 0 gives the identity encoding.
+inline int host_g2_mul(const uint8_t q192[192], const uint8_t k32[32], uint8_t out192[192]) {
+  g2_affine q;
+  if (!g2_decode192(q, q192) || !g2_on_curve(q)) return BP_ERR_BAD_POINT;
+  if (!fr_is_canonical(k32)) return BP_ERR_BAD_SCALAR;
+  uint32_t k[8];
+  memcpy(k, k32, 32);
+  g2_encode192(out192, g2_to_affine(g2_mul(q, k, 8)));
+  return BP_OK;
+}
 
 }  // namespace bp

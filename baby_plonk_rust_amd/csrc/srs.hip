@@ -85,6 +85,12 @@ int srs_from_projective_run(bp_ctx* ctx, const g1_proj* d_in, size_t n, g1_affin
   BP_HIP(ctx, hipGetLastError());
   return BP_OK;
 }
+int srs_scale_run(bp_ctx* ctx, const g1_affine* d_pts, const fr_t* d_scalars, size_t n, g1_proj* d_out) {
+  if (n == 0) return BP_OK;
+  hipLaunchKernelGGL(srs_scale, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_pts, d_scalars, n, d_out);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
 int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t first, size_t n, g1_affine* d_out) {
   if (n == 0) return BP_OK;
   // the table of the generator's multiples (1 MiB) lives in a workspace of the context: built by the first call, in stream order

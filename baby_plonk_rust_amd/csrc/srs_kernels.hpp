@@ -5,10 +5,12 @@
 //                    s_i = a + i*d (synthetic benchmark points)
 //   srs_decode48 / srs_subgroup_check / srs_encode48 : the 48-byte compressed encoding (g1.rs:221-244, 326-390) and the subgroup
 //                    test (g1.rs:401-411), arithmetic in g1_check.hpp
+//   srs_scale      : out_i = k_i P_i, one variable-base multiplication per lane (a ceremony contribution, bp_srs_scale)
 #pragma once
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "g1_check.hpp"
+#include "g1_mul_split28.hpp"
 #include "g1_ntt.hpp"
 
 namespace bp {
@@ -177,6 +179,20 @@ __global__ void __launch_bounds__(256) srs_from_projective(const g1_proj* __rest
     if (inf) { r.x = Fp::zero(); r.y = Fp::zero(); }
     out[i] = r;
   }
+}
+
+// ---- a different scalar for every point (bp_srs_scale) ---------------------------------------------------------------------------
+// out[i] = k_i * pts[i] as a G1Projective image for srs_from_projective: one lane per point, the 128-step joint double-and-add of
+// g1_mul_split28 (the body and the launch bounds of verify_seg_mul).  k_i: Montgomery, any value < q (0 gives the identity);
+// pts[i]: a point of the prime-order subgroup -- the host runs srs_subgroup_check first -- or the identity (0, 0), which stays the
+// identity (0 : 1 : 0), z = 0.
+__global__ void __launch_bounds__(64) srs_scale(const g1_affine* __restrict__ pts, const fr_t* __restrict__ scalars, size_t n,
+                                                 g1_proj* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr_t k = scalars[i];
+  Fr::from_mont(k, k);
+  out[i] = g1_proj_from_28(g1_mul_split28(pts[i], k));
 }
 
 // ---- fixed-base generation (round 4) --------------------------------------------------------------------------------------------

@@ -12,8 +12,9 @@
 // Projective points between the kernels are 42 words (x | y | z, 14 limbs each) stored word-major: word w of element i sits at
 // w * count + i, so the lanes of a wave read and write neighbouring addresses.
 //
-// The multiplication.  g1_mul_split28 writes k = k1 x^2 + k0 (scalar_split.hpp) and runs ONE joint double-and-add over
-// P, [x^2] P = (beta x, -y) and their sum: 128 steps of one doubling and one complete addition.  g1_mul_plain28 is the
+// The multiplication.  g1_mul_split28 (g1_mul_split28.hpp: srs_scale runs it too) writes k = k1 x^2 + k0 (scalar_split.hpp) and
+// runs ONE joint double-and-add over P, [x^2] P = (beta x, -y) and their sum: 128 steps of one doubling and one complete addition.
+// g1_mul_plain28 is the
 // 255-step double-and-add it is measured against (docs/EXPERIMENTS.md).  The split form is exact only where the endomorphism is
 // [x^2], that is inside the prime-order subgroup: proof points are subgroup-checked in stage 3, the verifier key's are not, so the
 // host tests those eight points once per call and sends the shared-base terms through the plain form if one of them fails.
@@ -22,6 +23,7 @@
 #pragma once
 #include "g1_28.hpp"
 #include "g1_check.hpp"
+#include "g1_mul_split28.hpp"
 #include "scalar_split.hpp"
 #include "verify_kernels.hpp"
 
@@ -50,63 +52,8 @@ __device__ __forceinline__ g1_proj28 seg_load_pt(const uint32_t* __restrict__ ba
   seg_load_coord(p.z.l, base, count, i, 2);
   return p;
 }
-__device__ __forceinline__ C28 seg_one28() {
-  C28 r;
-#pragma unroll
-  for (int i = 0; i < N28; i++) r.l[i] = One28::limb(i);
-  return r;
-}
 
-// k P for a canonical k < 2^255 and an affine P of the prime-order subgroup, or the identity (0, 0)
-__device__ __forceinline__ g1_proj28 g1_mul_split28(const g1_affine& p, const fr_t& k) {
-  uint32_t k0[4], k1[4];
-  scalar_split_x2(k0, k1, k.l);
-  const bool id = g1_affine_is_identity(p);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    k0[i] = id ? 0u : k0[i];
-    k1[i] = id ? 0u : k1[i];
-  }
-  fp_t beta, bx;
-#pragma unroll
-  for (int i = 0; i < 12; i++) beta.l[i] = fp_beta_canonical(i);
-  Fp::to_mont(beta, beta);
-  Fp::mul(bx, p.x, beta);
-  const F28n y0 = fp_to_28(p.y);
-  const C28 one = seg_one28();
-  g1_proj28 P0, P1, P01;                                        // P, [x^2] P = -phi(P) = (beta x, -y), and their sum
-  P0.x = widen28<C28>(fp_to_28(p.x));
-  P0.y = widen28<C28>(y0);
-  P0.z = one;
-  P1.x = widen28<C28>(fp_to_28(bx));
-  P1.y = widen28<C28>(pt_y_signed(y0, true));
-  P1.z = one;
-  g1_add28(P01, P0, P1);
-  g1_proj28 acc = g1_identity28();
-#pragma unroll 1
-  for (int step = 0; step < SCALAR_SPLIT_BITS; step++) {
-    const uint32_t sel = (k0[3] >> 31) | ((k1[3] >> 31) << 1);
-#pragma unroll
-    for (int i = 3; i > 0; i--) {
-      k0[i] = (k0[i] << 1) | (k0[i - 1] >> 31);
-      k1[i] = (k1[i] << 1) | (k1[i - 1] >> 31);
-    }
-    k0[0] <<= 1;
-    k1[0] <<= 1;
-    g1_double28(acc, acc);
-    g1_proj28 op;                                               // 0: the identity, 1: P, 2: [x^2] P, 3: both
-#pragma unroll
-    for (int i = 0; i < N28; i++) {
-      op.x.l[i] = sel == 1 ? P0.x.l[i] : sel == 2 ? P1.x.l[i] : sel == 3 ? P01.x.l[i] : 0u;
-      op.y.l[i] = sel == 1 ? P0.y.l[i] : sel == 2 ? P1.y.l[i] : sel == 3 ? P01.y.l[i] : one.l[i];
-      op.z.l[i] = sel == 3 ? P01.z.l[i] : sel == 0 ? 0u : one.l[i];
-    }
-    g1_add28(acc, acc, op);
-  }
-  return acc;
-}
-
-// the same product by 255 doublings and selected mixed additions: any affine point of the curve, or the identity (0, 0)
+// the product of g1_mul_split28 by 255 doublings and selected mixed additions: any affine point of the curve, or the identity (0, 0)
 __device__ __forceinline__ g1_proj28 g1_mul_plain28(const g1_affine& p, const fr_t& k) {
   const bool id = g1_affine_is_identity(p);
   const F28n x = fp_to_28(p.x);

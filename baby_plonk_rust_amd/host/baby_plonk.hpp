@@ -11,10 +11,12 @@
 //   root_of_unity / roots_of_unity (src/utils.rs:39-52)     root_of_unity / roots_of_unity
 //   Polynomial + operators (src/polynomial.rs:14-380)       Polynomial
 //   Setup::generate_srs / commit (src/setup.rs:12-37)       Setup
+//   (no counterpart: ceremony files)                        Setup::check_powers / from_lagrange_points / contribute / verify_contribution
 //   CommonPreprocessedInput (src/program.rs:34-50)          CommonPreprocessedInput
 //   Prover::new / prove (src/prover.rs:64-175)              Prover::prove_with_blinding (blinders are an argument)
 //   Proof (src/verifier.rs:23-40)                           Proof (624 bytes: 9 compressed points, 6 scalars)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdlib>
@@ -128,6 +130,20 @@ enum class Basis { Lagrange = BP_BASIS_LAGRANGE, Monomial = BP_BASIS_MONOMIAL };
 
 using G1 = std::array<uint8_t, 96>;   // G1Affine::to_uncompressed (g1.rs:246-260)
 using G1Compressed = std::array<uint8_t, 48>;   // G1Affine::to_compressed (g1.rs:221-244)
+using G2 = std::array<uint8_t, 192>;  // G2Affine::to_uncompressed (g2.rs:284-303): x_2 = tau G2 of a setup (setup.rs:20)
+// host-side: k G2 and k Q for a canonical little-endian k (bp_g2_mul_generator, bp_g2_mul)
+inline G2 g2_mul_generator(const std::array<uint8_t, 32>& k_le) {
+  G2 out{};
+  int rc = bp_g2_mul_generator(k_le.data(), out.data());
+  if (rc != BP_OK) throw Panic(rc, "g2_mul_generator: scalar not canonical");
+  return out;
+}
+inline G2 g2_mul(const G2& q, const std::array<uint8_t, 32>& k_le) {
+  G2 out{};
+  int rc = bp_g2_mul(q.data(), k_le.data(), out.data());
+  if (rc != BP_OK) throw Panic(rc, "g2_mul: point off the curve or scalar not canonical");
+  return out;
+}
 
 // src/utils.rs:39-43
 inline Scalar root_of_unity(uint64_t group_order) {
@@ -264,7 +280,75 @@ class Setup {
     uint64_t h = 0;
     c.check(bp_srs_generate(c.raw(), powers, tau_le.data(), &h), "generate_srs");
     if (tables) (void)bp_srs_precompute(c.raw(), h, 0);      // an optimisation (windows x 128 B per point of HBM): commits work without it
-    return Setup(h, c);
+    Setup s(h, c);
+    s.set_x_2(g2_mul_generator(tau_le));                                                                              // setup.rs:20
+    return s;
+  }
+  // x_2 = tau G2: known to generate_srs, handed over with a loaded ceremony file (set_x_2); the verdict methods below need it
+  void set_x_2(const G2& x_2) { x2_ = x_2; has_x2_ = true; }
+  bool has_x_2() const { return has_x2_; }
+  const G2& x_2() const {
+    if (!has_x2_) throw Panic(BP_ERR_INVALID_ARG, "the setup has no x_2 (set_x_2)");
+    return x2_;
+  }
+  size_t len() const {
+    size_t n = 0;
+    ctx_->check(bp_srs_len(ctx_->raw(), handle_, &n), "srs_len");
+    return n;
+  }
+  static constexpr size_t npos = SIZE_MAX;
+  // Are the points G, tau G, tau^2 G, ... for the tau of x_2 (bp_srs_check_powers)?  npos, or the lowest bad index: 0 when P_0 is
+  // not the generator (generator == true), i >= 1 when P_i != tau P_{i-1}.  rho: 32 canonical little-endian bytes the caller drew
+  // AFTER the points were fixed, 128 bits of entropy or more.
+  size_t check_powers(const std::array<uint8_t, 32>& rho_le, bool generator = true) const {
+    size_t bad = npos;
+    int rc = bp_srs_check_powers(ctx_->raw(), handle_, x_2().data(), rho_le.data(), BP_FR_BYTES_LE, generator ? BP_SRS_CHECK_GENERATOR : 0u, &bad);
+    if (rc == BP_ERR_BAD_POINT && bad != npos) return bad;
+    ctx_->check(rc, "check_powers");
+    return npos;
+  }
+  // A Lagrange Setup from SHIPPED Lagrange points (a power of two of them), adopted only after they were checked against the powers
+  // of `powers` (bp_srs_adopt_lagrange: two MSMs and a transform, no pairing).  Same context and x_2 as `powers`.  Wrong points are a
+  // Panic whose text names the lowest wrong index.
+  static Setup from_lagrange_points(const std::vector<G1>& points, const Setup& powers, const std::array<uint8_t, 32>& rho_le, bool tables = true) {
+    if (points.empty() || (points.size() & (points.size() - 1))) throw Panic(BP_ERR_NOT_POW2, "from_lagrange_points: not a power of two of points");
+    Context& c = *powers.ctx_;
+    uint32_t log_n = 0;
+    while (((size_t)1 << log_n) < points.size()) log_n++;
+    uint64_t loaded = 0, h = 0;
+    c.check(bp_srs_load(c.raw(), points[0].data(), points.size(), &loaded), "from_lagrange_points: points");
+    int rc = bp_srs_adopt_lagrange(c.raw(), loaded, powers.handle_, log_n, rho_le.data(), BP_FR_BYTES_LE, &h, nullptr);
+    const std::string why = rc == BP_OK ? "" : bp_last_error(c.raw());
+    bp_srs_free(c.raw(), loaded);
+    if (rc != BP_OK) throw Panic(rc, "from_lagrange_points: " + why);
+    if (tables) (void)bp_srs_precompute(c.raw(), h, 0);
+    Setup s(h, c);
+    if (powers.has_x2_) s.set_x_2(powers.x2_);
+    return s;
+  }
+  // One contribution to the ceremony: points s^i P_i (bp_srs_scale, one multiplication per GPU lane) and x_2' = s x_2.
+  Setup contribute(const std::array<uint8_t, 32>& s_le, bool tables = true) const {
+    const size_t n = len();
+    const std::vector<Scalar> pows = powers_of(Scalar::from_bytes(s_le), n, *ctx_);
+    uint64_t h = 0;
+    ctx_->check(bp_srs_scale(ctx_->raw(), handle_, pows.data(), n, BP_FR_MONT, 0, &h, nullptr), "contribute");
+    if (tables) (void)bp_srs_precompute(ctx_->raw(), h, 0);
+    Setup out(h, *ctx_);
+    if (has_x2_) out.set_x_2(g2_mul(x2_, s_le));
+    return out;
+  }
+  // Is this Setup `previous` after ONE contribution whose secret s was published as s_2 = s G2?  Equal lengths, a clean
+  // check_powers here, and pairing(P'_1, G2) == pairing(P_1, s_2) (bp_pairing_check_host with s_2 in the place of x_2).
+  bool verify_contribution(const Setup& previous, const G2& s_2, const std::array<uint8_t, 32>& rho_le) const {
+    const size_t n = len();
+    if (n != previous.len() || n < 2 || check_powers(rho_le) != npos) return false;
+    uint8_t pair[192], verdict = 0;
+    size_t bad = 0;
+    previous.ctx_->check(bp_srs_export(previous.ctx_->raw(), previous.handle_, 1, 1, pair), "verify_contribution");
+    ctx_->check(bp_srs_export(ctx_->raw(), handle_, 1, 1, pair + 96), "verify_contribution");
+    int rc = bp_pairing_check_host(s_2.data(), pair, 1, 0, &verdict, nullptr, &bad);
+    if (rc != BP_OK) throw Panic(rc, "verify_contribution: s_2 or a point rejected");
+    return verdict == 1;
   }
   std::vector<G1> powers_of_x() const {
     size_t n = 0;
@@ -335,8 +419,24 @@ class Setup {
 
  private:
   Setup(uint64_t h, Context& c) : handle_(h), ctx_(&c) {}
+  // s^0 .. s^(n-1) in log2(n) doubling steps through the library's scalar product (no field arithmetic of this header's own):
+  // out[0 .. m) known -> out[m .. 2m) = out[0 .. m) * s^m
+  static std::vector<Scalar> powers_of(const Scalar& s, size_t n, Context& c) {
+    std::vector<Scalar> out(n);
+    if (n) out[0] = Scalar::from_u64(1);
+    Scalar sm = s;                                              // s^m
+    for (size_t m = 1; m < n; m *= 2) {
+      const size_t cnt = std::min(m, n - m);
+      c.check(bp_poly_scalar_op(c.raw(), out.data(), cnt, BP_BASIS_MONOMIAL, sm.l.data(), 2, BP_FR_MONT, out.data() + m), "contribute: powers");
+      const Scalar prev = sm;
+      c.check(bp_poly_scalar_op(c.raw(), prev.l.data(), 1, BP_BASIS_MONOMIAL, prev.l.data(), 2, BP_FR_MONT, sm.l.data()), "contribute: powers");
+    }
+    return out;
+  }
   uint64_t handle_;
   Context* ctx_;
+  G2 x2_{};
+  bool has_x2_ = false;
 };
 
 // src/program.rs:34-50: selector and permutation polynomials in the Lagrange basis

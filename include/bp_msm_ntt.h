@@ -586,6 +586,65 @@ int  bp_kzg_verify_reduce(bp_ctx* ctx, const uint8_t* commitments96, size_t m, s
 /* Milliseconds of the last opening's two stages -- values and quotient; the commit -- and of the last bp_kzg_verify_reduce. */
 int  bp_kzg_last_stats(bp_ctx* ctx, float ms[3]);
 
+/* ---- the structure of an SRS: powers of one tau, Lagrange points that belong to them, a ceremony contribution ----
+ * bp_srs_load* and bp_srs_check_subgroup say that every point is a point of G1; nothing there says that the points are
+ * G, tau G, tau^2 G, ... for ONE tau, or that x_2 is that tau in G2.  The calls below do, without knowing tau.
+ *
+ * bp_srs_powers_reduce: out192 = A || B (the record of bp_pairing_check) with
+ *   A = sum_{i < n_pairs} rho^i P_{first+i}        B = sum_{i < n_pairs} rho^i P_{first+i+1}
+ * Every pair satisfies P_{i+1} = tau P_i exactly when pairing(A, x_2) == pairing(B, G2Affine::generator()); if one pair does not,
+ * a rho drawn AFTER the points were fixed, with 128 bits of entropy or more, hides it with probability at most n_pairs / 2^127.  The
+ * two pairings stay with the caller, as with bp_verify_reduce.  Two MSMs (at `first` and `first + 1`, through the SRS's tables where
+ * it has them, over every shard of a bp_init_multi context) against ONE vector rho^i made on the device.
+ *   first + n_pairs + 1 > srs_len: BP_ERR_INVALID_ARG.  n_pairs == 0: BP_OK, A = B = identity.  A Lagrange SRS: BP_ERR_BASIS.
+ *   rho32 in scalar_fmt: a canonical-bytes value >= q is BP_ERR_BAD_SCALAR; rho < 2 is BP_ERR_INVALID_ARG (rho = 1 lets errors cancel,
+ *   rho = 0 looks at one pair). */
+int  bp_srs_powers_reduce(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n_pairs, const void* rho32, int scalar_fmt,
+                          uint8_t out192[192]);
+/* The verdict: one reduce over all srs_len - 1 pairs and one pairing check on the host (the code of bp_pairing_check_host; x_2 is
+ * decoded, curve- and subgroup-checked: a rejected x_2 is BP_ERR_BAD_POINT with *first_bad = SIZE_MAX, an identity x_2
+ * BP_ERR_INVALID_ARG).  BP_OK with *first_bad = SIZE_MAX: the points are the powers of the tau of x_2 (up to (srs_len - 1) / 2^127).
+ * BP_ERR_BAD_POINT otherwise, with *first_bad = the lowest i >= 1 such that P_i != tau P_{i-1} relative to x_2 (bp_last_error names
+ * it), found by bisection over the prefixes [0, k) of the pairs against the rho^i already on the device: a call makes at most
+ * 2 + ceil(log2(srs_len)) reduces and as many pairings, whatever it finds (bp_srs_check_last_stats).  A wrong x_2 fails every pair:
+ * *first_bad = 1.  checks & BP_SRS_CHECK_GENERATOR: P_0 must be G1Affine::generator() (a ceremony's first point; compared first, on
+ * the host): else *first_bad = 0.  Any other bit of checks is BP_ERR_INVALID_ARG.  srs_len <= 1 has no pair: BP_OK.  rho32 and the
+ * basis rule as bp_srs_powers_reduce.  first_bad may be NULL.  Blocking. */
+#define BP_SRS_CHECK_GENERATOR 2u
+int  bp_srs_check_powers(bp_ctx* ctx, uint64_t srs_handle, const uint8_t x2_192[192], const void* rho32, int scalar_fmt,
+                         uint32_t checks, size_t* first_bad);
+/* reduces (for bp_srs_adopt_lagrange: comparisons of two MSMs), host pairings and host wall-clock milliseconds of the last
+ * bp_srs_check_powers or bp_srs_adopt_lagrange on this ctx.  Any pointer may be null. */
+int  bp_srs_check_last_stats(bp_ctx* ctx, uint32_t* reduces, uint32_t* pairings, float* ms);
+/* A Lagrange-basis SRS that was SHIPPED (the Ethereum KZG ceremony's G1 points; an exported bp_srs_lagrange) instead of computed:
+ * `points` is a Monomial-tagged handle of exactly 2^log_n points from any loader (another length: BP_ERR_LENGTH), `powers` a
+ * Monomial handle of at least 2^log_n points (fewer: BP_ERR_INVALID_ARG) that bp_srs_check_powers has accepted.  With v_i = rho^i and
+ * c = i_ntt_381(v), the points are the Lagrange points of the powers exactly when sum_i v_i points_i == sum_j c_j powers_j as group
+ * elements (both sides commit to the polynomial with values v): two MSMs and one transform, no pairing, no x_2, error probability
+ * at most 2^log_n / 2^127 for a rho drawn after the points were fixed.  On success *lagrange_handle is a NEW handle -- a device-to-
+ * device copy of the points tagged BP_BASIS_LAGRANGE with this log_n, in every respect what bp_srs_lagrange returns -- and both
+ * sources are untouched.  On failure BP_ERR_BAD_POINT, no handle, and *first_bad (may be NULL) = the lowest wrong index, found by
+ * the bisection of bp_srs_check_powers with v zeroed from k on (one transform and two MSMs per step, the same bound on the steps).
+ * A Lagrange handle on either side: BP_ERR_BASIS.  log_n > 24: BP_ERR_TOO_LARGE.  rho32 as bp_srs_powers_reduce.  Blocking. */
+int  bp_srs_adopt_lagrange(bp_ctx* ctx, uint64_t points_handle, uint64_t powers_handle, uint32_t log_n, const void* rho32,
+                           int scalar_fmt, uint64_t* lagrange_handle, size_t* first_bad);
+/* out_i = k_i * P_i for all n == srs_len points (another n: BP_ERR_LENGTH) as a new SRS of the same basis and log_n: one variable-
+ * base multiplication per GPU lane.  With k_i = s^i this is a contribution to a ceremony, P_i <- s^i P_i (x_2 <- s x_2: bp_g2_mul).
+ * The source is ALWAYS subgroup-tested first (the test of bp_srs_check_subgroup): the multiplication is the 128-step split form,
+ * exact only inside the prime-order subgroup, and a contribution to points outside it means nothing -- a point outside is
+ * BP_ERR_BAD_POINT with its index in *first_bad (may be NULL; SIZE_MAX otherwise) and no handle.  An identity point stays the
+ * identity; k_i = 0 gives the identity.  scalars: n values in scalar_fmt, in host memory or (scalars_on_device != 0) in HBM of the
+ * primary device; a canonical-bytes value >= q is BP_ERR_BAD_SCALAR, no handle.  On a bp_init_multi context every shard scales its
+ * own range with its slice of the scalars, and the result is sharded like the source.  Blocking. */
+int  bp_srs_scale(bp_ctx* ctx, uint64_t srs_handle, const void* scalars, size_t n, int scalar_fmt, int scalars_on_device,
+                  uint64_t* out_handle, size_t* first_bad);
+/* HIP-event milliseconds of the last bp_srs_scale on this ctx: the subgroup test, the multiplications (srs_scale), the normalisation;
+ * summed over the shards of a bp_init_multi context (all 0 after a call refused for its length). */
+int  bp_srs_scale_last_stats(bp_ctx* ctx, float stage_ms[3]);
+/* Host-side, no context: out = k * Q in G2 for a canonical little-endian k (k >= q: BP_ERR_BAD_SCALAR).  Q is decoded and curve-
+ * checked (BP_ERR_BAD_POINT), not subgroup-checked; an identity Q or k = 0 gives the identity encoding. */
+int  bp_g2_mul(const uint8_t q192[192], const uint8_t k32[32], uint8_t out192[192]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -514,6 +514,12 @@ class Context:
         self.check(self._lib.bp_kzg_last_stats(self._h, ms), "bp_kzg_last_stats")
         return dict(zip(("values_quotient_ms", "commit_ms", "reduce_ms"), [float(v) for v in ms]))
 
+    def kzg_open_all_stats(self):
+        """milliseconds of the four stages of the last Setup.open_all on this context; table_ms is 0 when the table was there"""
+        ms = (C.c_float * 4)()
+        self.check(self._lib.bp_kzg_open_all_last_stats(self._h, ms), "bp_kzg_open_all_last_stats")
+        return dict(zip(("table_ms", "field_ms", "toeplitz_ms", "final_ms"), [float(v) for v in ms]))
+
     # ---- the structure of an SRS (capi_srs_check.hip) ----
     def srs_powers_reduce(self, handle, rho, first=0, n_pairs=None):
         """bp_srs_powers_reduce: (A96, B96) = (sum_i rho^i P_{first+i}, sum_i rho^i P_{first+i+1}) over n_pairs pairs (default: all
@@ -1114,6 +1120,32 @@ class Setup:
         c.check(fn(c._h, self.handle, ptrs, lens, k, ps[0].basis, z.ctypes.data, None if nu is None else nu.ctypes.data, FR_MONT,
                    ys.ctypes.data, w.ctypes.data), "Setup.open")
         return ys, bytes(w)
+
+    def prepare_open_all(self, group_order):
+        """build and keep the table open_all needs for this group_order (bp_srs_open_all_prepare: 2 * group_order points of HBM,
+        freed with the SRS; another group_order replaces it).  Optional: open_all builds it on first use."""
+        if group_order < 1 or group_order & (group_order - 1):
+            raise BpError(-2, "Setup.prepare_open_all", "group_order %d is not a power of two" % group_order)
+        c = self.ctx
+        c.check(c._lib.bp_srs_open_all_prepare(c._h, self.handle, group_order.bit_length() - 1), "Setup.prepare_open_all")
+
+    def open_all(self, poly, group_order=None):
+        """ALL group_order KZG proofs of one Polynomial or DevicePolynomial on its domain, in one call (bp_kzg_open_all /
+        bp_kzg_open_all_device): returns (ys [n, 4] uint64, proofs [n, 96] uint8) with ys[i] = f(w^i) and proofs[i] the proof of
+        that opening, w = root_of_unity(n).  A Monomial polynomial has at most n coefficients (group_order=None: the next power of
+        two), a Lagrange one exactly n values; this Setup must hold the powers of tau (n - 1 of them or more).  Claim i is then
+        Opening(commitment, w^i, ys[i:i+1], None, bytes(proofs[i]))."""
+        c = self.ctx
+        n = group_order
+        if n is None:
+            n = len(poly) if poly.basis == BASIS_LAGRANGE else max(1, 1 << max(len(poly) - 1, 0).bit_length())
+        if n < 1 or n & (n - 1):
+            raise BpError(-2, "Setup.open_all", "group_order %d is not a power of two" % n)
+        ys, proofs = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 96), dtype=np.uint8)
+        head = (c._h, self.handle, poly._ptr() if len(poly) else None, len(poly), poly.basis)
+        fn = getattr(c._lib, "bp_kzg_open_all" + poly._SUFFIX)
+        c.check(fn(*head, *poly._FMT, n.bit_length() - 1, ys.ctypes.data, proofs.ctypes.data), "Setup.open_all")
+        return ys, proofs
 
     def opening_pairing_inputs(self, openings, weights=None, checks=0):
         """the claims of a list of Opening records (one polynomial count for all) reduced to (A96, B96): they hold iff

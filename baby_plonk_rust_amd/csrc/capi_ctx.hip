@@ -324,6 +324,7 @@ void bp_destroy(bp_ctx* ctx) {
     if (kv.second.d_points) (void)hipFree(kv.second.d_points);
     if (kv.second.d_points28) (void)hipFree(kv.second.d_points28);
     if (kv.second.d_table) (void)hipFree(kv.second.d_table);
+    if (kv.second.d_open_all) (void)hipFree(kv.second.d_open_all);
   }
   for (auto& kv : ctx->circuits) circuit_release(kv.second);
   for (auto& kv : ctx->ntt_tables) {

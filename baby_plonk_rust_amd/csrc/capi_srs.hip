@@ -73,6 +73,7 @@ int srs_free_one(bp_ctx* ctx, uint64_t handle) {
   BP_HIP(ctx, hipFree(e->d_points));
   BP_HIP(ctx, hipFree(e->d_points28));
   if (e->d_table) BP_HIP(ctx, hipFree(e->d_table));
+  if (e->d_open_all) BP_HIP(ctx, hipFree(e->d_open_all));
   ctx->srs.erase(handle);
   return BP_OK;
 }

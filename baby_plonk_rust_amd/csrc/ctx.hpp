@@ -55,6 +55,10 @@ struct SrsEntry {
   // (bp_srs_lagrange; n_global == 2^log_n).  Every shard's entry carries both.
   int basis = BP_BASIS_MONOMIAL;
   uint32_t log_n = 0;
+  // bp_srs_open_all_prepare / bp_kzg_open_all: DFT_2n(S^) of this SRS for n = 2^open_all_log_n (kzg_open_all.hpp), 2n affine points on
+  // the context's own device (a group: held by the leader's entry only); nullptr until the first call, replaced by another log_n
+  g1_affine* d_open_all = nullptr;
+  uint32_t open_all_log_n = 0;
 };
 
 // preprocessed circuit of the native prover (prover.hip): CommonPreprocessedInput (program.rs:34-50) resident in HBM,
@@ -139,6 +143,10 @@ struct bp_ctx {
   // bp_kzg_open(_device): values + quotient | commit; bp_kzg_verify_reduce: the whole reduce; kzg_roots_*: the domain whose roots
   // the workspace "kzg.roots" holds
   float kzg_ms[3] = {0, 0, 0};
+  // bp_kzg_open_all(_device): table build (0: it was there) | field work | Toeplitz transform | final transform, normalisation, encoding
+  float kzg_open_all_ms[4] = {0, 0, 0, 0};
+  const void* open_all_tw_ptr = nullptr;             // the workspace "kzg.oa_tw" holds the twiddles of both lengths for this log_n
+  uint32_t open_all_tw_log_n = 0;
   // bp_srs_check_powers / bp_srs_adopt_lagrange: reduces (adopt: comparisons of two MSMs) and host pairings of the last call and its
   // host wall time; bp_srs_scale: subgroup test | srs_scale | normalisation of the last call (HIP events; a group: the sum over its shards)
   uint32_t srs_check_reduces = 0, srs_check_pairings = 0;
@@ -195,7 +203,9 @@ struct bp_ctx {
   uint64_t comm_collectives = 0;                   // collectives this context has enqueued on its communicator(s) (bp_comm_stats)
   bool comm_init_stuck = false;                    // an ncclCommInitRank of this context ran into the bound: its helper thread is still inside RCCL
   uint64_t free_bytes_probe = 0;                   // tests only (bpx_set_free_bytes_probe): the free-memory reading bp_srs_precompute decides on; 0 = hipMemGetInfo
-  std::vector<float> g1_ntt_pass_ms;               // g1_ntt_run: HIP-event time of each pass of the last transform on this context
+  // g1_ntt_run: HIP-event time of each pass of the last transform on this context; bp_kzg_open_all: of the passes of its transforms in
+  // the order they ran (the table's log_n + 1 when it was built, the Toeplitz transform's log_n + 1, the final transform's log_n)
+  std::vector<float> g1_ntt_pass_ms;
   bool gen_table_ready = false;                    // srs_generate_run: the generator's multiples were built into gen_table_ptr
   const void* gen_table_ptr = nullptr;
   void* pinned = nullptr;                          // small pinned staging buffer (window sums etc.)
@@ -355,6 +365,13 @@ int srs_generate_run(bp_ctx* ctx, const fr_t& a, const fr_t& d, int mode, size_t
 int srs_scale_run(bp_ctx* ctx, const g1_affine* d_pts, const fr_t* d_scalars, size_t n, g1_proj* d_out);
 // the inverse transform over G1 of d_in[0 .. 2^log_n) (g1_ntt.hpp) -> affine points; waits for the stream
 int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_out);
+// all n = 2^log_n proofs on the domain (kzg_open_all.hpp), 1 <= log_n < G1_NTT_MAX_LOG; both wait for the stream and append their pass
+// times to ctx->g1_ntt_pass_ms.  table: d_table[0 .. 2n) = DFT_2n(S^) of d_srs[0 .. n - 1).  proofs: d_out[0 .. n) from the table and
+// d_sc[0 .. 2n) = N^-1 DFT_2n(c^) (Montgomery); `mid` is recorded between the Toeplitz and the final transform.
+int open_all_table_run(bp_ctx* ctx, const g1_affine* d_srs, uint32_t log_n, g1_affine* d_table);
+int open_all_proofs_run(bp_ctx* ctx, const g1_affine* d_table, const fr_t* d_sc, uint32_t log_n, g1_affine* d_out, hipEvent_t mid);
+int open_all_twiddles_run(bp_ctx* ctx, uint32_t log_n);      // the buffers and twiddle tables of this log_n, made unless they are there (enqueued)
+int open_all_chat_run(bp_ctx* ctx, uint32_t log_n, const fr_t* d_f, size_t n_values, const fr_t& scale, fr_t* d_out);      // d_out[t] = scale c^_t, t < 2n
 // kzg.hip: the values y_j = f_j(z) (host_y, count of them) and the quotient (sum_j nu^j f_j - sum_j nu^j y_j) / (x - z) of count
 // <= 16 HBM-resident Montgomery polynomials, in the form they are held in; *d_q is a workspace of the context, *nq its length.
 // nu_pows: nu^0 .. nu^(count-1).  Lagrange: every column has 2^log_n values, the quotient too.  Monomial: nq = max_j n_j - 1 (0: no quotient).

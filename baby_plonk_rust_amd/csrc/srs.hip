@@ -1,5 +1,6 @@
 // srs.hip -- host drivers of the SRS kernels (srs_kernels.hpp).
 #include <stdlib.h>
+#include <string.h>
 
 #include <utility>
 #include <vector>
@@ -150,6 +151,112 @@ int g1_ntt_run(bp_ctx* ctx, const g1_affine* d_in, uint32_t log_n, g1_affine* d_
     BP_HIP(ctx, hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
     ctx->g1_ntt_pass_ms.push_back(ms);
   }
+  return BP_OK;
+}
+
+// ---- all n proofs of a polynomial on its domain (kzg_open_all.hpp) ------------------------------------------------------------------
+// The two projective buffers (2n points each; the Lagrange transform's, grown) and the twiddles of both lengths: omega_2n^k, k < n, then omega_n^k, k < n / 2.
+struct OpenAllBufs {
+  g1_proj *a, *b;
+  fr_t *tw_big, *tw_small;
+};
+static int open_all_bufs(bp_ctx* ctx, uint32_t log_n, OpenAllBufs* o) {
+  const size_t n = (size_t)1 << log_n;
+  fr_t* tw;
+  BP_TRY(ws_get(ctx, "srs.g1_ntt_a", 2 * n * sizeof(g1_proj), (void**)&o->a));
+  BP_TRY(ws_get(ctx, "srs.g1_ntt_b", 2 * n * sizeof(g1_proj), (void**)&o->b));
+  BP_TRY(ws_get(ctx, "kzg.oa_tw", (n + n / 2 + 1) * sizeof(fr_t), (void**)&tw));
+  o->tw_big = tw;
+  o->tw_small = tw + n;
+  if (ctx->open_all_tw_ptr == (const void*)tw && ctx->open_all_tw_log_n == log_n) return BP_OK;      // kept between calls of one size
+  ctx->open_all_tw_ptr = nullptr;
+  fr_t omega;
+  (void)host_root_of_unity(omega, (uint64_t)(2 * n));
+  BP_TRY(roots_run(ctx, omega, n, o->tw_big));
+  (void)host_root_of_unity(omega, (uint64_t)n);
+  BP_TRY(roots_run(ctx, omega, n / 2, o->tw_small));
+  ctx->open_all_tw_ptr = tw;
+  ctx->open_all_tw_log_n = log_n;
+  return BP_OK;
+}
+int open_all_twiddles_run(bp_ctx* ctx, uint32_t log_n) {
+  OpenAllBufs w;
+  return open_all_bufs(ctx, log_n, &w);
+}
+// passes 1 .. log_len - 1 behind a pass 0 that wrote *cur (the other buffer: *oth); on return *cur holds the result.  ev[s + 1] is
+// recorded behind pass s (ev[0]: the caller's, in front of pass 0).
+static int open_all_rest_run(bp_ctx* ctx, uint32_t log_len, const fr_t* tw, g1_proj** cur, g1_proj** oth, hipEvent_t* ev) {
+  const size_t half = (size_t)1 << (log_len - 1);
+  const dim3 grid((unsigned)((half + 255) / 256));
+  BP_HIP(ctx, hipGetLastError());                        // pass 0's launch
+  BP_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+  for (uint32_t s = 1; s < log_len; s++) {
+    hipLaunchKernelGGL(g1_ntt_pass<false>, grid, dim3(256), 0, ctx->stream, log_len, s, (const g1_affine*)nullptr, (const g1_proj*)*cur, *oth, tw, Fr::zero());
+    BP_HIP(ctx, hipGetLastError());
+    BP_HIP(ctx, hipEventRecord(ev[s + 1], ctx->stream));
+    std::swap(*cur, *oth);
+  }
+  return BP_OK;
+}
+static int open_all_pass_times(bp_ctx* ctx, hipEvent_t* ev, uint32_t passes) {
+  for (uint32_t s = 0; s < passes; s++) {
+    float ms = 0;
+    BP_HIP(ctx, hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
+    ctx->g1_ntt_pass_ms.push_back(ms);
+  }
+  return BP_OK;
+}
+// d_table[0 .. 2n) = DFT_2n(S^) of the first n - 1 points of d_srs, affine, natural order.  Waits for the stream; its log_n + 1 pass
+// times are appended to ctx->g1_ntt_pass_ms.  1 <= log_n < G1_NTT_MAX_LOG.
+int open_all_table_run(bp_ctx* ctx, const g1_affine* d_srs, uint32_t log_n, g1_affine* d_table) {
+  const size_t n = (size_t)1 << log_n;
+  OpenAllBufs w;
+  BP_TRY(open_all_bufs(ctx, log_n, &w));
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "kzg.oa_table", log_n + 2, hipEventDefault, &ev));
+  g1_proj *cur = w.a, *oth = w.b;
+  BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+  hipLaunchKernelGGL(g1_ntt_table_pass0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, log_n, d_srs, cur);
+  BP_TRY(open_all_rest_run(ctx, log_n + 1, w.tw_big, &cur, &oth, ev));
+  BP_TRY(srs_from_projective_run(ctx, cur, 2 * n, d_table));
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  return open_all_pass_times(ctx, ev, log_n + 1);
+}
+// d_out[i] = proof i, affine: the Toeplitz transform over d_table with the per-entry scalars d_sc = N^-1 DFT_2n(c^) (Montgomery), the
+// final transform over its first n outputs, the normalisation.  `mid` is recorded between the two transforms.  Waits for the stream;
+// appends the log_n + 1 and log_n pass times.
+int open_all_proofs_run(bp_ctx* ctx, const g1_affine* d_table, const fr_t* d_sc, uint32_t log_n, g1_affine* d_out, hipEvent_t mid) {
+  const size_t n = (size_t)1 << log_n;
+  OpenAllBufs w;
+  BP_TRY(open_all_bufs(ctx, log_n, &w));
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "kzg.oa_proofs", 2 * log_n + 3, hipEventDefault, &ev));
+  hipEvent_t* ev2 = ev + log_n + 2;
+  g1_proj *cur = w.a, *oth = w.b;
+  BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+  const dim3 grid0((unsigned)((n + 255) / 256));
+#ifdef BP_EXPERIMENT
+  const char* mul = knob("BP_OPEN_ALL_MUL");              // experiment knob: split28 = the 128-step multiplication of srs_scale in pass 0
+  if (mul && !strcmp(mul, "split28")) hipLaunchKernelGGL(g1_ntt_toeplitz_pass0_split28, grid0, dim3(256), 0, ctx->stream, log_n + 1, d_table, d_sc, cur);
+  else
+#endif
+    hipLaunchKernelGGL(g1_ntt_toeplitz_pass0, grid0, dim3(256), 0, ctx->stream, log_n + 1, d_table, d_sc, cur);
+  BP_TRY(open_all_rest_run(ctx, log_n + 1, w.tw_big, &cur, &oth, ev));
+  BP_HIP(ctx, hipEventRecord(mid, ctx->stream));
+  BP_HIP(ctx, hipEventRecord(ev2[0], ctx->stream));
+  hipLaunchKernelGGL(g1_ntt_final_pass0, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, ctx->stream, log_n, (const g1_proj*)cur, oth);
+  std::swap(cur, oth);                                   // cur: what pass 0 wrote; oth: h, free from pass 1 on
+  BP_TRY(open_all_rest_run(ctx, log_n, w.tw_small, &cur, &oth, ev2));
+  BP_TRY(srs_from_projective_run(ctx, cur, n, d_out));
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  BP_TRY(open_all_pass_times(ctx, ev, log_n + 1));
+  return open_all_pass_times(ctx, ev2, log_n);
+}
+// d_out[t] = scale c^_t, t < 2n (srs_kernels.hpp: open_all_chat_fill)
+int open_all_chat_run(bp_ctx* ctx, uint32_t log_n, const fr_t* d_f, size_t n_values, const fr_t& scale, fr_t* d_out) {
+  const size_t N = (size_t)2 << log_n;
+  hipLaunchKernelGGL(open_all_chat_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, log_n, d_f, n_values, scale, d_out);
+  BP_HIP(ctx, hipGetLastError());
   return BP_OK;
 }
 

@@ -6,12 +6,15 @@
 //   srs_decode48 / srs_subgroup_check / srs_encode48 : the 48-byte compressed encoding (g1.rs:221-244, 326-390) and the subgroup
 //                    test (g1.rs:401-411), arithmetic in g1_check.hpp
 //   srs_scale      : out_i = k_i P_i, one variable-base multiplication per lane (a ceremony contribution, bp_srs_scale)
+//   g1_ntt_pass    : one pass of the inverse transform over G1 (bp_srs_lagrange); g1_ntt_table_pass0 / _toeplitz_pass0 / _final_pass0 and
+//                    open_all_chat_fill: pass 0 of the three transforms behind bp_kzg_open_all and its scalar layout (kzg_open_all.hpp)
 #pragma once
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "g1_check.hpp"
 #include "g1_mul_split28.hpp"
 #include "g1_ntt.hpp"
+#include "kzg_open_all.hpp"
 
 namespace bp {
 
@@ -300,6 +303,59 @@ __global__ void __launch_bounds__(256) g1_ntt_pass(uint32_t log_n, uint32_t s, c
   const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= ((uint64_t)1 << (log_n - 1))) return;
   g1_ntt_pass_at<FIRST>(log_n, s, b, in, src, dst, tw, n_inv);
+}
+
+// ---- all n proofs of a polynomial on its domain (kzg_open_all.hpp): pass 0 of its three transforms --------------------------------
+// One lane per butterfly, as above; every later pass of the three is g1_ntt_pass<false>.  Bounds: the table pass reads srs[k] only for
+// k <= n - 2 (open_all_shat), the Toeplitz pass table[j] and sc[j] for j < 2n, the final pass h[j] for j < n; each writes slots < len.
+__global__ void __launch_bounds__(256) g1_ntt_table_pass0(uint32_t log_n, const g1_affine* __restrict__ srs, g1_proj* __restrict__ dst) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= ((uint64_t)1 << log_n)) return;                           // len / 2 = n butterflies
+  open_all_table_pass0_at(log_n, b, srs, dst);
+}
+// the scalar differs from lane to lane, so the branch on its bits in g1_ntt_mul diverges inside a wave: every step then costs the
+// doubling and the addition (DESIGN.md 4.8 has the pass times)
+__global__ void __launch_bounds__(256) g1_ntt_toeplitz_pass0(uint32_t log_len, const g1_affine* __restrict__ table, const fr_t* __restrict__ sc,
+                                                               g1_proj* __restrict__ dst) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= ((uint64_t)1 << (log_len - 1))) return;
+  open_all_toeplitz_pass0_at(log_len, b, table, sc, dst);
+}
+#ifdef BP_EXPERIMENT
+// The alternative multiplication of the Toeplitz pass, experiment build only (BP_OPEN_ALL_MUL=split28; tools/kzg_open_all_timing.py
+// times it beside the default): g1_mul_split28, the 128-step joint double-and-add of srs_scale on 28-bit limbs, with no branch on a
+// scalar bit.  Valid here because the table's entries are DFT images of subgroup points, hence subgroup points.  Device only, so
+// the host loop of kzg_open_all.hpp cannot run it; DESIGN.md 4.8 has both pass times and why the default is g1_ntt_mul.
+__global__ void __launch_bounds__(256) g1_ntt_toeplitz_pass0_split28(uint32_t log_len, const g1_affine* __restrict__ table, const fr_t* __restrict__ sc,
+                                                                       g1_proj* __restrict__ dst) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= ((uint64_t)1 << (log_len - 1))) return;
+  const G1NttStep st = g1_ntt_step(log_len, 0, b);
+  const uint64_t j0 = g1_ntt_bitrev(st.i0, log_len), j1 = g1_ntt_bitrev(st.i1, log_len);
+  fr_t k;
+  Fr::from_mont(k, sc[j1]);
+  g1_proj v = g1_proj_from_28(g1_mul_split28(table[j1], k));
+  Fr::from_mont(k, sc[j0]);
+  g1_proj u = g1_proj_from_28(g1_mul_split28(table[j0], k));
+  g1_ntt_butterfly(u, v);
+  dst[st.i0] = u;
+  dst[st.i1] = v;
+}
+#endif
+__global__ void __launch_bounds__(256) g1_ntt_final_pass0(uint32_t log_n, const g1_proj* __restrict__ h, g1_proj* __restrict__ dst) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= ((uint64_t)1 << (log_n - 1))) return;
+  open_all_final_pass0_at(log_n, b, h, dst);
+}
+// out[t] = scale * c^_t, t < 2n (Montgomery): the coefficients f[0 .. n_values) (n_values <= n, the rest zero) laid out for the
+// convolution, with N^-1 of the inverse G1 transform already on them
+__global__ void __launch_bounds__(256) open_all_chat_fill(uint32_t log_n, const fr_t* __restrict__ f, size_t n_values, fr_t scale, fr_t* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ((uint64_t)2 << log_n)) return;
+  const uint64_t k = open_all_chat(log_n, t);
+  fr_t v = Fr::zero();
+  if (k != OPEN_ALL_NONE && k < n_values) Fr::mul(v, f[k], scale);
+  out[t] = v;
 }
 
 }  // namespace bp

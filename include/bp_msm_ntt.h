@@ -586,6 +586,37 @@ int  bp_kzg_verify_reduce(bp_ctx* ctx, const uint8_t* commitments96, size_t m, s
 /* Milliseconds of the last opening's two stages -- values and quotient; the commit -- and of the last bp_kzg_verify_reduce. */
 int  bp_kzg_last_stats(bp_ctx* ctx, float ms[3]);
 
+/* ---- all n = 2^log_n opening proofs of ONE polynomial on its domain (Feist, Khovratovich) ----
+ * Proof i opens f at w^i, w = root_of_unity(n): pi_i = [(f(tau) - f(w^i)) / (tau - w^i)] G.  The n quotient commitments are one
+ * Toeplitz product of the coefficients with the first n - 1 SRS points (a cyclic convolution of length 2n: one Fr transform, one
+ * transform over G1 whose first pass multiplies entry j of a prepared table by its own scalar) followed by one DFT of length n over
+ * G1: O(n log n) group operations instead of the n MSMs of n calls of bp_kzg_open.
+ *   srs_handle   a powers-of-tau SRS (BP_BASIS_MONOMIAL; a Lagrange handle is BP_ERR_BASIS).  Only its first n - 1 points are used;
+ *                n - 1 > srs_len is BP_ERR_LENGTH.  An unknown handle is BP_ERR_INVALID_ARG.
+ *   log_n        log_n >= 24 is BP_ERR_TOO_LARGE (the transform of 2n points is the limit).  log_n == 0: one proof, the identity, and
+ *                the value f_0; no kernel runs.
+ *   poly, basis  BP_BASIS_MONOMIAL: n_values <= n coefficients (more: BP_ERR_LENGTH; fewer: zero-padded; 0: the zero polynomial, poly
+ *                may then be NULL).  BP_BASIS_LAGRANGE: exactly n values f(w^i) (BP_ERR_LENGTH otherwise), transformed internally by
+ *                one inverse NTT; the returned values are then the input itself.
+ *   values       n scalars f(w^i) in scalar_fmt, or NULL.   proofs96: n x 96 bytes, natural order (identity = 0x40, zeros).
+ * A BP_FR_BYTES_LE input >= q is BP_ERR_BAD_SCALAR.  Null pointers and a bad format or basis are BP_ERR_INVALID_ARG.  A rejected call
+ * writes nothing.  Blocking, ordered on the context's stream.  A bp_init_multi context collects the points on its primary device (as
+ * bp_srs_lagrange does) and runs there.
+ *
+ * bp_srs_open_all_prepare builds and keeps the table DFT_2n(S^) for this SRS and log_n (2n x 96 bytes of HBM, released by
+ * bp_srs_free; a later call with another log_n replaces it).  Optional: bp_kzg_open_all builds it on first use. */
+int  bp_srs_open_all_prepare(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n);
+int  bp_kzg_open_all(bp_ctx* ctx, uint64_t srs_handle, const void* poly, size_t n_values, int basis, int scalar_fmt,
+                     uint32_t log_n, void* values, uint8_t* proofs96);
+/* The same for a polynomial resident in HBM on the context's primary device (Montgomery); values_mont_host: n Montgomery scalars in
+ * HOST memory, or NULL. */
+int  bp_kzg_open_all_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_poly, size_t n_values, int basis,
+                            uint32_t log_n, void* values_mont_host, uint8_t* proofs96);
+/* HIP-event ms of the last bp_kzg_open_all(_device): table build (0 when it was already there), field work (with the twiddle tables
+ * of the G1 transforms when the table was there but the context has no twiddles for this log_n; a table build makes them itself),
+ * Toeplitz transform, final transform + normalisation + encoding. */
+int  bp_kzg_open_all_last_stats(bp_ctx* ctx, float stage_ms[4]);
+
 /* ---- the structure of an SRS: powers of one tau, Lagrange points that belong to them, a ceremony contribution ----
  * bp_srs_load* and bp_srs_check_subgroup say that every point is a point of G1; nothing there says that the points are
  * G, tau G, tau^2 G, ... for ONE tau, or that x_2 is that tau in G2.  The calls below do, without knowing tau.

@@ -141,9 +141,8 @@ static int msm_all_shards(bp_ctx* ctx, uint64_t srs_handle, size_t first, const 
 
 namespace bp {
 constexpr int MAX_LANES = 3;
-constexpr int MSM_BATCH_MAX = 4;          // = MSM_MAX_BATCH of msm_kernels.hpp (scalar vectors in one pipeline)
 
-// k commitments of HBM-resident coefficient vectors (on the leader) over the members of a group: per batch of up to MSM_BATCH_MAX
+// k commitments of HBM-resident coefficient vectors (on the leader) over the members of a group: per batch of up to MSM_MAX_BATCH
 // vectors every member receives its slice of each (peer copies behind the leader's event), runs ONE pipeline over the slices'
 // bucket sets and delivers one partial sum per vector; the host adds the members' partial sums.  BP_ERR_TOO_LARGE before anything
 // was launched = a member's batch does not fit one pipeline.
@@ -153,8 +152,8 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_
   const size_t R = sh.size(), n_global = sh[0].e->n_global;
   for (const SrsShard& s : sh)
     if (!s.e->d_table) return BP_ERR_TOO_LARGE;
-  for (int base = 0; base < k; base += MSM_BATCH_MAX) {
-    const int cnt = std::min(MSM_BATCH_MAX, k - base);
+  for (int base = 0; base < k; base += MSM_MAX_BATCH) {
+    const int cnt = std::min((int)MSM_MAX_BATCH, k - base);
     {
       DeviceGuard guard(ctx->device);
       BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on the leader's stream
@@ -167,8 +166,8 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_
       bp_ctx* m = sh[r].m;
       const SrsEntry* e = sh[r].e;
       DeviceGuard guard(m->device);
-      const fr_t* ptrs[MSM_BATCH_MAX];
-      size_t lens[MSM_BATCH_MAX], total = 0;
+      const fr_t* ptrs[MSM_MAX_BATCH];
+      size_t lens[MSM_MAX_BATCH], total = 0;
       for (int j = 0; j < cnt; j++) {
         const size_t nj = std::min(n[base + j], n_global);              // zip() truncation, msm.rs:29
         lens[j] = nj > e->first ? std::min(nj - e->first, e->n) : 0;
@@ -200,10 +199,10 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_
       used[r] = rcs[r] == BP_OK;
       rc = lift(ctx, m, rcs[r]);
     }
-    std::vector<g1_proj> part(R * MSM_BATCH_MAX);
+    std::vector<g1_proj> part(R * MSM_MAX_BATCH);
     over_members(ctx, R, [&](size_t r) { return (bool)used[r]; }, [&](size_t r) {
       DeviceGuard guard(sh[r].m->device);
-      rcs[r] = msm_finish(sh[r].m, pend[r], &part[r * MSM_BATCH_MAX]);
+      rcs[r] = msm_finish(sh[r].m, pend[r], &part[r * MSM_MAX_BATCH]);
     });
     for (size_t r = 0; r < R; r++)
       if (used[r] && rc == BP_OK) rc = lift(ctx, sh[r].m, rcs[r]);
@@ -211,7 +210,7 @@ static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_
     for (int j = 0; j < cnt; j++) {
       g1_proj acc = g1_identity();
       for (size_t r = 0; r < R; r++)
-        if (used[r]) g1_add(acc, acc, part[r * MSM_BATCH_MAX + j]);
+        if (used[r]) g1_add(acc, acc, part[r * MSM_MAX_BATCH + j]);
       out[base + j] = acc;
     }
   }
@@ -236,7 +235,7 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
   if (k <= 0) return BP_OK;
   SrsEntry* e;
   BP_TRY(srs_find(ctx, srs_handle, &e));
-  if (is_group(ctx) && k > 1 && e->d_table) {   // group: ONE pipeline per member over its slices of up to MSM_BATCH_MAX commitments
+  if (is_group(ctx) && k > 1 && e->d_table) {   // group: ONE pipeline per member over its slices of up to MSM_MAX_BATCH commitments
     const char* v = knob("BP_COMMIT_BATCH");
     if (!(v && *v == '0')) {
       int rc = commit_many_group_batched(ctx, srs_handle, d_coeffs, n, k, out);
@@ -272,10 +271,10 @@ int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, c
     for (int j = 0; j < k; j++) n_max = std::max(n_max, std::min(n[j], e->n));
     if (srs_tables_pay(*e, n_max) && v && *v == '1') {
       bool ok = true;
-      for (int base = 0; base < k && ok; base += (int)MSM_BATCH_MAX) {
-        const int cnt = std::min((int)MSM_BATCH_MAX, k - base);
-        const fr_t* ptrs[MSM_BATCH_MAX];
-        size_t lens[MSM_BATCH_MAX];
+      for (int base = 0; base < k && ok; base += (int)MSM_MAX_BATCH) {
+        const int cnt = std::min((int)MSM_MAX_BATCH, k - base);
+        const fr_t* ptrs[MSM_MAX_BATCH];
+        size_t lens[MSM_MAX_BATCH];
         for (int j = 0; j < cnt; j++) {
           ptrs[j] = d_coeffs[base + j];
           lens[j] = std::min(n[base + j], e->n);                        // zip() truncation, msm.rs:29

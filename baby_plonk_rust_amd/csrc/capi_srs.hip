@@ -366,9 +366,6 @@ static int srs_precompute_one(bp_ctx* ctx, SrsEntry* e, uint32_t c) {
   return BP_OK;
 }
 
-// fixed-base tables of width c (as bp_srs_precompute takes it) pay for an MSM of n points once the bucket adds outweigh the
-// fixed 2^c reduction
-static bool srs_width_pays(uint32_t c, size_t n) { return 8 * (uint64_t)n >= (1ull << c); }
 bool srs_tables_pay(const SrsEntry& e, size_t n) { return e.d_table && srs_width_pays(e.table_c, n); }
 
 int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
@@ -377,20 +374,7 @@ int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
   BP_TRY(srs_shards(ctx, srs_handle, &sh));
   const SrsEntry* lead = sh[0].e;
   uint32_t c = window_bits;
-  if (c == 0) {                       // auto, from the length of one shard (every shard of a group gets the same width)
-    uint32_t lg = 0;
-    const uint64_t n = lead->n;
-    while ((2ull << lg) <= n) lg++;                       // floor(log2 n)
-    if (lg >= 24) {                   // 12 windows: the 2^21-bucket tree (+0.8 ms) against n fewer additions (-1.8 ms at 2^24; a tie at 2^23)
-      c = 22;
-    } else if (lg >= 20) {            // 13 windows instead of 16: pays once the sort and the 2^19-bucket tree are small against
-      c = 20;                         // 3 x n additions (round 3: -3 % at 2^20, -6 % at 2^21, -12 % at 2^22; profiles/r03_window_width_ab.txt)
-    } else if (n >= (1u << 14)) {     // throughput regime: reduction work 2^c stays below the bucket-add work W * n
-      c = lg + 2 > 16 ? 16 : lg + 2;
-    } else {                          // latency regime (a few thousand points): every kernel is a dependent chain, and the
-      c = lg > 8 ? lg - 4 : 4;        // reduction tree has c - 1 levels -- measured optimum 2^10: 6, 2^12: 8
-    }
-  }
+  if (c == 0) c = srs_auto_width(lead->n);      // from the length of one shard (every shard of a group gets the same width)
   if (c != BP_SRS_TABLES_OFF && (c < 4 || c > 24))
     return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "window_bits must be 0 (auto), 1 (off) or 4..24");
   // Memory budget: the tables (rows x points x 128 B: 25.8 GB per GPU at 2^24 points) must fit beside whatever else lives on the
@@ -413,7 +397,7 @@ int bp_srs_precompute(bp_ctx* ctx, uint64_t srs_handle, uint32_t window_bits) {
       size_t free_b = 0, total_b = 0;
       BP_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
       if (ctx->free_bytes_probe) free_b = (size_t)ctx->free_bytes_probe;        // tests: the reading to decide on (bpx_set_free_bytes_probe below)
-      const size_t rows = srs_table_rows(cc);
+      const size_t rows = msm_windows(cc);
       size_t& need = per_device[s.m->device];
       size_t& old_bytes = held[s.m->device];
       if (e->d_table) old_bytes += (size_t)e->table_W * std::max<size_t>(e->n, 1) * sizeof(g1_affine28);

@@ -11,6 +11,7 @@
 #include "../../include/bp_msm_ntt.h"
 #include "g1.hpp"
 #include "g1_28.hpp"
+#include "msm_plan.hpp"
 #include "ntt_plan.hpp"
 #include "prover_host.hpp"
 
@@ -322,7 +323,7 @@ int msm_init_device(bp_ctx* ctx);
 int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out);
 int srs_tables_run(bp_ctx* ctx, const g1_affine* d_points, const g1_affine28* d_points28, size_t n, uint32_t c, g1_affine28** d_table,
                    uint32_t* windows);
-uint32_t srs_table_rows(uint32_t c);                 // rows of the fixed-base tables of window width c (msm.hip)
+MsmKnobs msm_knobs();                                // the BP_MSM_* variables (msm.hip); rows of the tables of width c: msm_windows(c), msm_plan.hpp
 int srs_to28_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28** d_out);
 int srs_to28_into(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28* d_out);      // the same into a buffer of the caller's, on ctx->stream
 int ntt_init_tables(bp_ctx* ctx);

@@ -3,7 +3,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
 #include <vector>
 
 #include "ctx.hpp"
@@ -11,117 +10,11 @@
 
 namespace bp {
 
-static uint32_t ilog2_floor(size_t n) {
-  uint32_t l = 0;
-  while ((n >> (l + 1)) != 0) l++;
-  return l;
-}
-// radix for table width c with W windows (R = 0: power-of-two windows); cached per width
-static const MsmRadix& msm_radix_for(uint32_t c, uint32_t W) {
-  static MsmRadix cache[MSM_MAX_TABLE_C + 1];
-  static bool done[MSM_MAX_TABLE_C + 1];
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!done[c]) {
-    done[c] = true;
-    // Widths from 21 bits only (2^20 allocated buckets and more).  Fewer live buckets save tree time only where a tree level runs for
-    // several wave rounds: at c = 22 (2^21 buckets, 2^24 points) the radix takes 0.3 ms off the 5.3-ms tail and 0.65 ms off the MSM; at
-    // c = 20 every wide level of the 2^19-bucket tree is ONE round of two waves per SIMD, a fifth of the workgroups leaving early frees
-    // no SIMD earlier, and the division costs msm_part_count 9 us: 2.60-2.64 against 2.63 ms, no gain (profiles/r06_tail_ab.txt).
-    // Experiment build: BP_MSM_RADIX=0 keeps power-of-two windows everywhere, BP_MSM_RADIX_FROM moves the threshold.
-    if (knob_u32("BP_MSM_RADIX", 1, 0, 1) != 0 && c >= knob_u32("BP_MSM_RADIX_FROM", 21, 8, 30)) cache[c] = msm_radix_compute(c, W);
-  }
-  return cache[c];
-}
-// live buckets of table width c (the prefix of the 2^(c-1) allocated ones that digits can reach)
-uint32_t msm_table_radix(uint32_t c, uint32_t W) { return msm_radix_for(c, W).R; }
+static_assert(sizeof(proj28_slot) == MSM_SLOT_BYTES, "msm_plan.hpp sizes the workspaces by this");
 
-// Window width: minimise W * (n + 2 * 2^(c-1)) (bucket adds + reduction adds).  Per-window bucket sets (any point set) are
-// bounded by the 128 KiB LDS histogram of one window (c <= 16); with fixed-base tables wider windows go through the
-// partitioned sort (plan.parts > 1), up to MSM_MAX_TABLE_C.
-// table_c != 0: the SRS carries fixed-base window tables built for that width (row length table_stride)
-static void make_plan(MsmPlan& plan, size_t n, uint32_t table_c, size_t table_stride, uint32_t J = 1) {
-  memset(&plan, 0, sizeof plan);
-  plan.n = (uint32_t)n;
-  plan.J = J;
-  plan.nj[0] = (uint32_t)n;
-  uint32_t c = n < 32 ? 4 : ilog2_floor(n) - 3;
-  if (c < 4) c = 4;
-  if (c > MSM_MAX_C) c = MSM_MAX_C;
-  c = knob_u32("BP_MSM_C", c, 2, MSM_MAX_C);
-  if (c > (uint32_t)MSM_MAX_C) c = MSM_MAX_C;          // per-window bucket sets: one LDS histogram per window
-  if (table_c) c = table_c;                          // tables: up to MSM_MAX_TABLE_C through the partitioned sort
-  if (c < 2) c = 2;
-  // digits d_w = ((k + bias) >> c*w & mask) - 2^(c-1) with bias = sum_w 2^(c-1) 2^(cw); needs k + bias < 2^(cW)
-  // for every k < q.  Take W = ceil(256 / c) and check the bound with the real q; add a window if it fails.
-  static const uint32_t q_minus_1[8] = {0x00000000u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                                        0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-  // Windows 0..W-2 are signed: d_w = ((k + bias) >> cw & mask) - 2^(c-1), bias = sum_{w<W-1} 2^(c-1) 2^(cw).
-  // The top window is unsigned (digit = remaining high bits, carry included) and must fit a bucket index,
-  // i.e. be <= 2^(c-1) for every k < q.  Smallest such W:
-  uint32_t W = (255 + c - 1) / c;
-  if (W < 2) W = 2;
-  for (;;) {
-    uint32_t bias[10] = {0};
-    for (uint32_t w = 0; w + 1 < W; w++) {
-      uint32_t bit = c * w + c - 1;
-      if (bit < 320) bias[bit >> 5] |= 1u << (bit & 31);
-    }
-    uint64_t carry = 0;
-    uint32_t sum[11] = {0};
-    for (int j = 0; j < 10; j++) {
-      carry += (uint64_t)(j < 8 ? q_minus_1[j] : 0u) + bias[j];
-      sum[j] = (uint32_t)carry;
-      carry >>= 32;
-    }
-    // top digit of the largest scalar: (q - 1 + bias) >> c (W - 1), as an exact 320-bit shift
-    const uint32_t o = c * (W - 1);
-    bool ok = o < 288;
-    uint64_t top = 0;
-    for (int bit = 319; bit >= (int)o && ok; bit--) {
-      if ((sum[bit >> 5] >> (bit & 31)) & 1) {
-        if (bit - (int)o >= 32) ok = false; else top |= 1ull << (bit - o);
-      }
-    }
-    if (ok && top <= (1ull << (c - 1))) {
-      memcpy(plan.bias, bias, sizeof plan.bias);
-      break;
-    }
-    W++;
-  }
-  if (table_c) {                                     // fixed-base tables: the radix need not be a power of two
-    const MsmRadix& rx = msm_radix_for(c, W);
-    if (rx.R) {
-      plan.radix = rx.R;
-      memcpy(plan.radix_m, rx.m, sizeof plan.radix_m);
-      memcpy(plan.bias, rx.bias, sizeof plan.bias);
-    }
-  }
-  plan.c = c;
-  plan.W = W;
-  plan.B = 1u << (c - 1);
-  plan.total = table_c ? J * plan.B : W * plan.B;
-  plan.wbuckets = table_c ? 0 : plan.B;
-  plan.wpoints = table_c ? (uint32_t)table_stride : 0;
-  plan.parts = plan.B <= (1u << MSM_HIST_LOG) ? 1 : plan.B >> MSM_HIST_LOG;
-  const uint64_t entries = (uint64_t)W * n * J;
-  // entries per lane: the kernel runs 2 waves per SIMD = 131072 lanes at a time and every lane does the same work, so the
-  // lane count should land just under a whole number of such rounds.  (A power-of-two chunk wasted up to a third of the last
-  // round whenever windows * n was not a power of two: 13 or 15 windows.)  Measured with tables (r02_chunk_rounds_ab.txt):
-  //   up to 2^20 entries (2^16 points): half a round -- chains of 16 leave two partials per bucket instead of eight (0.531 -> 0.482 ms);
-  //   up to 2*10^7 entries (2^20 points and the prover's 2^20 + 6): ONE round (2^20: 3.13 -> 3.03 ms, 2^18 1.004 -> 0.979, 2^17 0.723 -> 0.675);
-  //   beyond: two rounds (2^21 .. 2^24 are equal or 1-3 % better with two: the second round evens out the lanes' finish times).
-  // Per-window buckets (no tables) are short: cap the chunk at 64.
-  const uint32_t chunk_cap = table_c ? 1024u : 64u;
-  uint32_t chunk;
-  if (table_c && entries <= (1u << 20)) chunk = (uint32_t)(entries >> 16);
-  else if (table_c && entries <= 20000000u) chunk = (uint32_t)((entries + 131071) / 131072);      // 2^24 and a little more: the prover's SRS has n + 6 points
-  else chunk = (uint32_t)((entries + 262143) / 262144);
-  if (chunk < 4) chunk = 4;
-  if (chunk > chunk_cap) chunk = chunk_cap;
-  plan.chunk = knob_u32("BP_MSM_CHUNK", chunk, 1, 1024);
-  plan.lanes = knob_u32("BP_MSM_CHUNK", 0, 1, 1024) ? 0u : (uint32_t)((entries + plan.chunk - 1) / plan.chunk);      // = the host's n_chunks
-}
+// the only reader of the BP_MSM_* variables (experiment build; the shipped library's knob() answers nullptr, so every default stays).
+// The tables of an SRS and the MSMs over them must see the same BP_MSM_RADIX / BP_MSM_RADIX_FROM.
+MsmKnobs msm_knobs() { return msm_knobs_read(knob_u32); }
 
 // unsaturated copy of an SRS (128-byte slots) (allocated here, owned by the SRS entry)
 int srs_to28_run(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28** d_out) {
@@ -139,17 +32,12 @@ int srs_to28_into(bp_ctx* ctx, const g1_affine* d_in, size_t n, g1_affine28* d_o
   return BP_OK;
 }
 
-// table[w * n + i] = 2^(c w) P_i; row 0 is the unsaturated SRS copy itself
-uint32_t srs_table_rows(uint32_t c) {
-  MsmPlan plan;
-  make_plan(plan, 1, c, 1);
-  return plan.W;
-}
-
+// table[w * n + i] = 2^(c w) P_i (R^w P_i with a radix); row 0 is the unsaturated SRS copy itself
 int srs_tables_run(bp_ctx* ctx, const g1_affine* d_points, const g1_affine28* d_points28, size_t n, uint32_t c, g1_affine28** d_table,
                    uint32_t* windows) {
-  const uint32_t W = srs_table_rows(c);
-  const uint32_t radix = msm_table_radix(c, W);       // rows R^w P_i where the MSM cuts radix-R digits (MsmPlan::radix)
+  const uint32_t W = msm_windows(c);
+  const MsmRadix* rx = msm_table_radix(c, msm_knobs());
+  const uint32_t radix = rx ? rx->R : 0u;             // rows R^w P_i where the MSM cuts radix-R digits (MsmPlan::radix)
   if ((uint64_t)W * n >= (1ull << 31))
     return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "fixed-base tables: windows * points >= 2^31");
   g1_affine28* t = nullptr;
@@ -180,45 +68,52 @@ static g1_proj slot_to_proj(const proj28_slot* slot) {
 
 // dynamic-LDS limits are per function AND per device: set them for every context at creation (bp_init), after hipSetDevice
 int msm_init_device(bp_ctx* ctx) {
-  // these two also hold a few KiB of static LDS: the dynamic limit must leave room for it
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_final<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_final<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_long_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_long_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_long_scatter<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_radix_long_scatter<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-  BP_HIP(ctx, hipFuncSetAttribute((const void*)msm_part_scatter<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  const struct { const void* kernel; size_t limit; } limits[] = {
+      {(const void*)msm_radix_scatter, MSM_LDS_RADIX_SCATTER},
+      {(const void*)msm_radix_final<false>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_radix_final<true>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_radix_long_count<false>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_radix_long_count<true>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_radix_long_scatter<false>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_radix_long_scatter<true>, MSM_LDS_RUN_HIST},
+      {(const void*)msm_part_scatter<false, false>, MSM_LDS_PART_SCATTER},
+      {(const void*)msm_part_scatter<false, true>, MSM_LDS_PART_SCATTER},
+      {(const void*)msm_part_scatter<true, false>, MSM_LDS_PART_SCATTER},
+      {(const void*)msm_part_scatter<true, true>, MSM_LDS_PART_SCATTER},
+  };
+  for (const auto& l : limits) BP_HIP(ctx, hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.limit));
   return BP_OK;
 }
 
-// scalars per workgroup of a pass that cuts digits from the scalars: `slice` doubled up to `limit` while that leaves at least `wgs` workgroups
-// and the pass's staging area (`staged` bytes per scalar, twice) stays within 64 KiB
-static uint32_t part_slice(uint32_t slice, uint32_t limit, uint32_t wgs, uint64_t scalars, uint64_t staged) {
-  while (slice < limit && 2 * slice * staged <= 65536 && (uint64_t)slice * wgs < scalars) slice <<= 1;
-  return slice;
+// device buffers of the bucket sort: the workspaces msm.ctl .. msm.run_long (keys / vals: msm.rkeys0 / 1, msm.rvals0 / 1)
+struct SortBufs {
+  uint32_t *ctl, *counts, *offsets, *cursors, *sorted, *tile_sums, *keys[2], *vals[2], *run_off, *run_cnt, *run_cur, *run_long;
+};
+
+// level 1 of either sort (MsmLevel1): 2^pb partitions cut straight from the scalars, their offsets to `off`, their records to keys / vals
+static void level1_launch(hipStream_t st, const MsmHostPlan& hp, const MsmScalars& scalars, int fmt, const SortBufs& b, uint32_t* off, uint32_t* keys,
+                          uint32_t* vals) {
+  const MsmLevel1& s = hp.l1;
+  hipLaunchKernelGGL(msm_part_count, dim3(s.n_slices1), dim3(s.count_threads), 0, st, scalars, fmt, hp.dev, s.slice1, s.pb, s.rb, b.ctl + 4, off, b.run_cur, b.ctl + 1);
+  const auto scatter = hp.packed ? (hp.flat ? msm_part_scatter<true, true> : msm_part_scatter<true, false>)
+                                 : (hp.flat ? msm_part_scatter<false, true> : msm_part_scatter<false, false>);
+  hipLaunchKernelGGL(scatter, dim3(s.n_slices), dim3(s.scatter_threads), s.part_lds, st, scalars, fmt, hp.dev, s.slice, s.pb, s.rb, hp.sort == 2 ? hp.vb : 0u, s.cap,
+                     b.run_cur, keys, vals);
 }
 
-// the partition sort behind its count pass, for one record form: the scatter, the final runs, the long runs among them
+// the final runs of either sort, for one record form: each sorted in one workgroup's histogram, the long runs among them slice-parallel
 template <bool PACKED>
-static void part_sort_launch(hipStream_t st, bool flat, uint32_t n_slices, unsigned threads, size_t part_lds, unsigned final_threads, size_t rhist,
-                             const MsmScalars& scalars, int fmt, const MsmPlan& plan, uint32_t slice, uint32_t pb, uint32_t rbits, uint32_t vb, uint32_t cap,
-                             uint32_t* cur, uint32_t* recs, uint32_t* rvals, uint32_t* roff, uint32_t* offsets, uint32_t* sorted, uint32_t* rlong_n,
-                             uint32_t* rlong_list, uint32_t* counts, uint32_t* cursors, uint32_t* run_ticket) {
-  const uint32_t n_final = 1u << pb, total = plan.total;
-  if (flat) hipLaunchKernelGGL((msm_part_scatter<PACKED, true>), dim3(n_slices), dim3(threads), part_lds, st, scalars, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-  else hipLaunchKernelGGL((msm_part_scatter<PACKED, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars, fmt, plan, slice, pb, rbits, vb, cap, cur, recs, rvals);
-  const RunRecords<PACKED> rr{recs, rvals, (1u << rbits) - 1u, PACKED ? vb : 0u};       // rvals: null with packed records
-  hipLaunchKernelGGL(msm_radix_final<PACKED>, dim3(n_final < 4096 ? n_final : 4096), dim3(final_threads), rhist, st, rr, roff, n_final, rbits, total, offsets,
-                     sorted, rlong_n, rlong_list, counts);
-  if (n_final > 1) {
-    const dim3 lgrid(64, n_final < 4 ? n_final : 4);
-    hipLaunchKernelGGL(msm_radix_long_count<PACKED>, lgrid, dim3(1024), rhist, st, rr, roff, n_final, rbits, total, rlong_n, rlong_list, counts, offsets,
-                       cursors, run_ticket);
-    hipLaunchKernelGGL(msm_radix_long_scatter<PACKED>, lgrid, dim3(1024), rhist, st, rr, roff, rbits, rlong_n, rlong_list, cursors, sorted);
+static void final_runs_launch(hipStream_t st, const MsmHostPlan& hp, const SortBufs& b, const uint32_t* keys, const uint32_t* vals, const uint32_t* off) {
+  const uint32_t total = hp.dev.total;
+  uint32_t *rlong_n = b.ctl + 2, *run_ticket = b.ctl + hp.run_ticket;
+  const RunRecords<PACKED> rr{keys, vals, (1u << hp.rbits) - 1u, PACKED ? hp.vb : 0u};       // vals: null with packed records
+  hipLaunchKernelGGL(msm_radix_final<PACKED>, dim3(hp.final_grid), dim3(hp.final_threads), hp.rhist, st, rr, off, hp.n_final, hp.rbits, total, b.offsets, b.sorted,
+                     rlong_n, b.run_long, b.counts);
+  if (hp.long_gx) {
+    const dim3 lgrid(hp.long_gx, hp.long_gy);
+    hipLaunchKernelGGL(msm_radix_long_count<PACKED>, lgrid, dim3(1024), hp.rhist, st, rr, off, hp.n_final, hp.rbits, total, rlong_n, b.run_long, b.counts, b.offsets,
+                       b.cursors, run_ticket);
+    hipLaunchKernelGGL(msm_radix_long_scatter<PACKED>, lgrid, dim3(1024), hp.rhist, st, rr, off, hp.rbits, rlong_n, b.run_long, b.cursors, b.sorted);
   }
 }
 
@@ -230,17 +125,16 @@ int msm_launch(bp_ctx* ctx, const g1_affine28* d_points28, size_t n, const fr_t*
 }
 
 // J scalar vectors against the same points in one pipeline (J > 1: fixed-base tables only, results in the pinned slot only);
-// vector j has n_each[j] scalars.  msm_finish then delivers J results.
+// vector j has n_each[j] scalars.  msm_finish then delivers J results.  Every decision is msm_plan's (msm_plan.hpp): this function
+// allocates by the plan's sizes and launches by its fields.
 int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, const fr_t* const* d_scalars_each, const size_t* n_each, int fmt,
                     uint32_t table_c, size_t table_stride, int slot, void* d_blob, MsmPending* out) {
   *out = MsmPending();
   out->blob = d_blob != nullptr;
-  if (J < 1 || J > MSM_MAX_BATCH || (J > 1 && (!table_c || d_blob)))
-    return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "MSM batch");
-  size_t n = 0;
-  for (uint32_t j = 0; j < J; j++) n = n_each[j] > n ? n_each[j] : n;
+  const MsmHostPlan hp = msm_plan(J, n_each, table_c, table_stride, d_blob != nullptr, msm_knobs());
+  if (hp.err == BP_ERR_INVALID_ARG) return BP_FAIL(ctx, hp.err, hp.what);       // a batch no pipeline takes: refused before anything else
   out->J = J;
-  if (n == 0) {
+  if (hp.empty) {
     if (d_blob) {
       MsmBlobHeader hdr;
       memset(&hdr, 0, sizeof hdr);
@@ -251,288 +145,112 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
     return BP_OK;
   }
   if (slot < 0 || slot >= MSM_SLOTS) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "MSM result slot");
-  if (n >= (1ull << 31)) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM length >= 2^31");
-  MsmPlan plan;
-  make_plan(plan, n, table_c, table_stride, J);
+  if (hp.err) return BP_FAIL(ctx, hp.err, hp.what);                             // too long, too many windows
+  const MsmPlan& plan = hp.dev;
   MsmScalars scalars_all;
-  for (uint32_t j = 0; j < MSM_MAX_BATCH; j++) {
-    plan.nj[j] = j < J ? (uint32_t)n_each[j] : 0u;
-    scalars_all.p[j] = j < J ? d_scalars_each[j] : nullptr;
-  }
-  if ((uint64_t)plan.W * n * J >= (1ull << 32))        // positions in the bucket-sorted list are 32-bit
-    return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM length * windows >= 2^32");
-  const uint32_t W = plan.W, total = plan.total, Wr = table_c ? J : W;   // Wr: bucket sets left after accumulation
-  const uint64_t max_entries = (uint64_t)W * n * J;
-  const uint64_t n_chunks = (max_entries + plan.chunk - 1) / plan.chunk;
-  // Bucket reduction: the bit-plane tree over one bucket set (tables) or, without tables, over the forest of the W bucket sets of 2^(c-1)
-  // buckets (running sums per window, a dependent chain of ~46 additions per lane, cost 0.57 ms at 2^20 points: docs/EXPERIMENTS.md Q), then
-  // two levels of the Horner form over each tree's c values (msm_planes_window_quads): `quads` values per window go to the host.
-  const uint32_t quads = table_c ? 1u : (plan.c + 2) / 4;          // ceil((c - 1) / 4); c = 2: one quad (A + T_0)
-  const uint32_t per_window = table_c ? plan.c : quads;     // slots per window that go to the host
-
-  uint32_t *counts, *offsets, *cursors, *sorted;
-  proj28_slot *bucket_sum, *partial, *window_sum;
-  // a bucket is "long" when it spans >= FIXUP_LONG chunks, so at most n_chunks / FIXUP_LONG + 1 buckets can be long
-  const uint32_t long_cap = (uint32_t)(n_chunks / FIXUP_LONG + 1);
-  // control words, zeroed by ONE memset per MSM: [0] long-bucket counter, [1] scalar status, [2] long-run counter of the sort,
-  // [4] ticket + [5 ..] partition sizes of msm_part_count, then one ticket per queued long bucket (msm_fixup_long)
-  // ... then one ticket per long RUN of the sort (msm_radix_long_count; at most 2^16 final runs).  The memset covers the words in use.
-  uint32_t* ctl;
-  const size_t ctl_fixed = 8 + PART_MAX + long_cap;
-  BP_TRY(ws_get(ctx, "msm.ctl", (ctl_fixed + 65536) * 4, (void**)&ctl));
-  uint32_t* run_ticket = ctl + ctl_fixed;
-  BP_TRY(ws_get(ctx, "msm.counts", (size_t)total * 4, (void**)&counts));        // bucket sizes of the sort's long runs
-  BP_TRY(ws_get(ctx, "msm.offsets", ((size_t)total + 1) * 4, (void**)&offsets));
-  BP_TRY(ws_get(ctx, "msm.cursors", (size_t)total * 4, (void**)&cursors));
-  uint32_t *long_count = ctl, *long_list, *long_ticket = ctl + 8 + PART_MAX;
-  BP_TRY(ws_get(ctx, "msm.long_list", (size_t)long_cap * 4, (void**)&long_list));
-  // slice sums of the buckets that take several workgroups: those have > FIXUP_LONG_SPLIT_FROM partials, so there are few of them, but the
-  // slot is addressed by the bucket's place in the list
-  proj28_slot* long_scratch;
-  BP_TRY(ws_get(ctx, "msm.long_scratch", (size_t)long_cap * FIXUP_LONG_SLICES * sizeof(proj28_slot), (void**)&long_scratch));
-  uint32_t* tile_sums;
-  BP_TRY(ws_get(ctx, "msm.tile_sums", 4096 * 4, (void**)&tile_sums));
-  BP_TRY(ws_get(ctx, "msm.sorted", max_entries * 4, (void**)&sorted));
-  BP_TRY(ws_get(ctx, "msm.bucket_sum", (size_t)total * sizeof(proj28_slot), (void**)&bucket_sum));
-  BP_TRY(ws_get(ctx, "msm.partial", 2 * n_chunks * sizeof(proj28_slot), (void**)&partial));
-  const uint32_t n_planes = Wr * per_window;        // tables: A and the c - 1 bit planes; else one sum per window
-  if (n_planes > (uint32_t)MSM_MAX_WINDOWS) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM windows");
-  proj28_slot* roots = nullptr;                     // table-free: the W roots (A, T_0 .. T_{c-2}) in front of the per-window Horner pass
-  if (!table_c) BP_TRY(ws_get(ctx, "msm.roots", (size_t)W * plan.c * sizeof(proj28_slot), (void**)&roots));
-  BP_TRY(ws_get(ctx, "msm.window_sum", (size_t)n_planes * sizeof(proj28_slot) + 16, (void**)&window_sum));     // + the status word
+  for (uint32_t j = 0; j < MSM_MAX_BATCH; j++) scalars_all.p[j] = j < J ? d_scalars_each[j] : nullptr;
+  SortBufs b = {};
+  uint32_t* long_list;
+  proj28_slot *long_scratch, *bucket_sum, *partial, *roots = nullptr, *window_sum, *tmp[2] = {nullptr, nullptr};
+  const struct { const char* name; size_t bytes; void** p; } buffers[] = {
+      {"msm.ctl", hp.ws.ctl, (void**)&b.ctl},
+      {"msm.counts", hp.ws.counts, (void**)&b.counts},
+      {"msm.offsets", hp.ws.offsets, (void**)&b.offsets},
+      {"msm.cursors", hp.ws.cursors, (void**)&b.cursors},
+      {"msm.long_list", hp.ws.long_list, (void**)&long_list},
+      {"msm.long_scratch", hp.ws.long_scratch, (void**)&long_scratch},
+      {"msm.tile_sums", hp.ws.tile_sums, (void**)&b.tile_sums},
+      {"msm.sorted", hp.ws.sorted, (void**)&b.sorted},
+      {"msm.bucket_sum", hp.ws.bucket_sum, (void**)&bucket_sum},
+      {"msm.partial", hp.ws.partial, (void**)&partial},
+      {"msm.roots", hp.ws.roots, (void**)&roots},
+      {"msm.window_sum", hp.ws.window_sum, (void**)&window_sum},
+      {"msm.rkeys0", hp.ws.rkeys0, (void**)&b.keys[0]},
+      {"msm.rvals0", hp.ws.rvals0, (void**)&b.vals[0]},
+      {"msm.rkeys1", hp.ws.rkeys1, (void**)&b.keys[1]},
+      {"msm.rvals1", hp.ws.rvals1, (void**)&b.vals[1]},
+      {"msm.run_off", hp.ws.run_off, (void**)&b.run_off},
+      {"msm.run_cnt", hp.ws.run_cnt, (void**)&b.run_cnt},
+      {"msm.run_cur", hp.ws.run_cur, (void**)&b.run_cur},
+      {"msm.run_long", hp.ws.run_long, (void**)&b.run_long},
+      {"msm.planes_tmp0", hp.ws.planes_tmp0, (void**)&tmp[0]},
+      {"msm.planes_tmp1", hp.ws.planes_tmp1, (void**)&tmp[1]},
+  };
+  for (const auto& w : buffers)
+    if (w.bytes) BP_TRY(ws_get(ctx, w.name, w.bytes, w.p));      // 0 bytes: this pipeline does not use it, the pointer stays null
   // pinned staging: MSM_SLOTS result areas of the largest possible size, so earlier pending results stay where they are
   constexpr size_t slot_bytes = (size_t)MSM_MAX_WINDOWS * sizeof(proj28_slot) + 16;
   uint8_t* h_base;
   BP_TRY(pinned_get(ctx, MSM_SLOTS * slot_bytes, (void**)&h_base));
   proj28_slot* h_windows = reinterpret_cast<proj28_slot*>(h_base + (size_t)slot * slot_bytes);
+  const uint32_t total = plan.total, n_planes = hp.n_planes;
+  uint32_t *offsets = b.offsets, *long_count = b.ctl, *status = b.ctl + 1, *long_ticket = b.ctl + 8 + PART_MAX;      // the control words: MsmHostPlan
   hipStream_t st = ctx->stream;
   BP_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  // Bucket sort, two builds: the partition sort (default wherever its 2^pb <= 2^11 partitions leave final runs
-  // that one workgroup sorts: up to ~5 * 10^7 entries) and the two-level radix sort (beyond; BP_MSM_SORT=1 forces it, 2 is the default).
-  uint32_t kb = 0;
-  while ((1ull << kb) < total) kb++;
-  uint32_t pb = 0;
-  // final runs of ~12-24 Ki entries; per-window bucket sets (no tables) take runs of half that length: 2^9 buckets of 16 entries per run sort
-  // faster than 2^9 buckets of 32 (tail 0.84 -> 0.80 ms at 2^20, 0.83 -> 0.80 at 2^18, 0.63 -> 0.60 at 2^16: tools/part_bits_probe.sh, round 5)
-  const uint64_t run_min = table_c ? 12288 : 6144;
-  while (pb < kb && (max_entries >> (pb + 1)) >= run_min) pb++;
-  pb = knob_u32("BP_MSM_RADIX_BITS", pb, 0, 16);
-  if (pb + MSM_HIST_LOG < kb) pb = kb - MSM_HIST_LOG;                   // a final run's buckets must fit one LDS histogram
-  if (pb > kb) pb = kb;
-  if (pb > 16) pb = 16;
-  if (pb > PART_MAX_BITS && (max_entries >> PART_MAX_BITS) <= 32768) pb = PART_MAX_BITS;     // final runs of up to 32 Ki entries are fine for one workgroup
-  if (pb + MSM_HIST_LOG < kb) pb = kb - MSM_HIST_LOG;
-  // record form of the partition sort: the packed word holds the bucket's low kb - pb bits, the sign and the entry (point or
-  // table index, vb - 1 bits).  Where a few more partitions make the record fit one word (c = 20 at 2^20: 2^12 instead of 2^10)
-  // they are taken: half the bytes through the scatter and the final sort (BP_MSM_PACKED=2 keeps the run length instead).
-  const uint64_t idx_max = (uint64_t)(n - 1) + (uint64_t)(W - 1) * plan.wpoints;
-  uint32_t vb = 1;
-  while ((idx_max >> (vb - 1)) != 0) vb++;                              // vb - 1 = bits of the largest entry, + 1 for the sign
-  const uint32_t packed_env = knob_u32("BP_MSM_PACKED", 1, 0, 2);
-  if (packed_env == 1 && kb + vb > 32 + pb && kb + vb - 32 <= PART_MAX_BITS && knob_u32("BP_MSM_RADIX_BITS", 99, 0, 16) == 99) pb = kb + vb - 32;
-  // 1: the two-level sort.  BP_MSM_SORT=1 takes it at sizes where the partition sort is the default (pb = 0 leaves no level to sort by: ignored)
-  const int sort_mode = ((knob_u32("BP_MSM_SORT", 2, 1, 2) == 1 && J == 1 && pb > 0) || pb > PART_MAX_BITS) ? 1 : 2;
-  if (sort_mode != 2 && J > 1) return BP_FAIL(ctx, BP_ERR_TOO_LARGE, "MSM batch too long for the partition sort");
-  const uint32_t rbits = kb - pb, n_final = 1u << pb;
-  // what this launch decided (bp_msm_last_path): host words only, copied into the context once everything is enqueued
-  uint32_t path[12] = {J, plan.c, W, plan.radix, (uint32_t)sort_mode, pb, 0u, 0u, 0u, 0u, 0u, plan.chunk};
-  const size_t rhist = ((size_t)1 << rbits) * 4;
-  BP_HIP(ctx, hipMemsetAsync(ctl, 0, (ctl_fixed + n_final) * 4, st));
-  uint32_t* rlong_n = ctl + 2;
-  if (sort_mode == 2) {
-    const bool packed = rbits + vb <= 32 && packed_env != 0;
-    const uint32_t rec_bytes = packed ? 4 : 8;
-    // scalars per workgroup: the staging area (slice * W records) within 64 KiB, and >= 512 workgroups where n allows
-    uint32_t slice = part_slice(64, 1024, 512, (uint64_t)n * J, (uint64_t)W * rec_bytes);
-    slice = knob_u32("BP_MSM_PART_SLICE", slice, 64, 4096);
-    if (slice < 64 || slice > 4096 || (uint64_t)slice * W * rec_bytes > 65536) slice = 64;
-    // Two-word records (2^21 .. 2^23 points at c = 20: bucket-low bits + sign + a 25..27-bit table index exceed one word): the 64-KiB rule leaves
-    // slices of 512 scalars, and a workgroup's fixed cost for its 2^12-entry tables (~12 us) then outweighs its records (~7 us).  A slice of
-    // 1 024 scalars stages 104 KiB; that fits beside the 48 KiB of tables when the per-record partition array of the flat write-out is dropped,
-    // i.e. with the partition-major write-out (BP_MSM_PART_WIDE8=0 keeps the 512-scalar slices).
-    const bool wide8 = !packed && slice == 512 && (uint64_t)1024 * 512 < (uint64_t)n * J && (size_t)3 * n_final * 4 + (size_t)1024 * W * 8 <= 156 * 1024 &&
-                       knob_u32("BP_MSM_PART_WIDE8", 1, 0, 1) != 0;
-    if (wide8) slice = 1024;
-    const uint32_t cap = slice * W, n_slices = (uint32_t)(((uint64_t)n * J + slice - 1) / slice);
-    const unsigned threads = slice >= 1024 ? 1024u : (slice <= 256 ? 256u : slice);
-    uint32_t *recs = nullptr, *rvals = nullptr, *roff, *cur, *rlong_list;
-    BP_TRY(ws_get(ctx, "msm.rkeys0", max_entries * 4, (void**)&recs));
-    if (!packed) BP_TRY(ws_get(ctx, "msm.rvals0", max_entries * 4, (void**)&rvals));
-    BP_TRY(ws_get(ctx, "msm.run_off", ((size_t)3 * n_final + 16) * 4, (void**)&roff));
-    BP_TRY(ws_get(ctx, "msm.run_cur", (size_t)n_final * 4, (void**)&cur));
-    BP_TRY(ws_get(ctx, "msm.run_long", ((size_t)n_final + 2) * 4, (void**)&rlong_list));
-    // the count pass keeps nothing per slice, so its slices are its own: fatter ones (~256 workgroups) flush their 2^pb partition
-    // sizes with a quarter of the global atomics (BP_MSM_COUNT_SLICE forces a size)
-    uint32_t slice1 = part_slice(slice, 8192, 256, (uint64_t)n * J, 0);      // measured at 2^20: 48 / 41 / 34 / 48 us at 1 024 / 2 048 / 4 096 / 8 192
-    slice1 = knob_u32("BP_MSM_COUNT_SLICE", slice1, 64, 65536);
-    const uint32_t n_slices1 = (uint32_t)(((uint64_t)n * J + slice1 - 1) / slice1);
-    hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb, rbits, ctl + 4, roff, cur, long_count + 1);
-    // a slice's share of a partition: long -> partition-major write-out, short -> one lane per record (BP_MSM_PART_FLAT = 0 / 1 forces)
-    const uint32_t flat_env = knob_u32("BP_MSM_PART_FLAT", 2, 0, 2);
-    const bool flat = wide8 ? false : (flat_env == 2 ? (cap >> pb) < 8 : flat_env == 1);
-    const size_t part_lds = (size_t)3 * n_final * 4 + (size_t)cap * rec_bytes + (flat ? (size_t)cap * 2 : 0);
-    path[6] = packed;
-    path[7] = flat;
-    path[8] = wide8;
-    // short final runs (2^12 runs of ~3 Ki records at c = 20): 512-lane workgroups (measured 70 / 60 / 72 us at 256 / 512 / 1024 lanes)
-    const unsigned final_threads = knob_u32("BP_MSM_FINAL_THREADS", (max_entries >> pb) <= 8192 ? 512 : 1024, 256, 1024) & ~63u;
-    (packed ? part_sort_launch<true> : part_sort_launch<false>)(st, flat, n_slices, threads, part_lds, final_threads, rhist, scalars_all, fmt, plan, slice, pb, rbits,
-                                                               vb, cap, cur, recs, rvals, roff, offsets, sorted, rlong_n, rlong_list, counts, cursors, run_ticket);
-  } else if (sort_mode == 1) {
-    const uint32_t lv[2] = {pb <= 8 ? pb : pb - pb / 2, pb <= 8 ? 0 : pb / 2};
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *cnt, *cur;
-    BP_TRY(ws_get(ctx, "msm.rkeys0", max_entries * 4, (void**)&keys[0]));
-    BP_TRY(ws_get(ctx, "msm.rvals0", max_entries * 4, (void**)&vals[0]));
-    if (pb) {
-      BP_TRY(ws_get(ctx, "msm.rkeys1", max_entries * 4, (void**)&keys[1]));
-      BP_TRY(ws_get(ctx, "msm.rvals1", max_entries * 4, (void**)&vals[1]));
-    }
-    uint32_t* roff;
-    BP_TRY(ws_get(ctx, "msm.run_off", ((size_t)3 * n_final + 16) * 4, (void**)&roff));
-    uint32_t* const run_off[2] = {roff + 4,                 // after level 1: 2^lv[0] + 1 entries
-                                  roff + 8 + n_final};      // after level 2: n_final + 1 entries
-    BP_TRY(ws_get(ctx, "msm.run_cnt", (size_t)n_final * 4, (void**)&cnt));
-    BP_TRY(ws_get(ctx, "msm.run_cur", (size_t)n_final * 4, (void**)&cur));
-    uint32_t* rlong_list;
-    BP_TRY(ws_get(ctx, "msm.run_long", ((size_t)n_final + 2) * 4, (void**)&rlong_list));
-    // Level 1 comes straight from the scalars, as the partition sort does it (msm_part_count + msm_part_scatter with two-word records into
-    // 2^lv[0] runs: no record pass, one array's traffic less -- 2^24 points, tail 5.87 -> 5.32 ms, profiles/r04_sort24_hybrid_ab.txt).
-    const uint32_t pb1 = lv[0], rb1 = kb - pb1;
-    {
-      const uint32_t slice = part_slice(64, 1024, 512, n, (uint64_t)W * 8), slice1 = part_slice(slice, 8192, 256, n, 0);
-      const uint32_t cap = slice * W, n_slices = (uint32_t)(((uint64_t)n + slice - 1) / slice);
-      const unsigned threads = slice >= 1024 ? 1024u : (slice <= 256 ? 256u : slice);
-      const uint32_t n_slices1 = (uint32_t)(((uint64_t)n + slice1 - 1) / slice1);
-      hipLaunchKernelGGL(msm_part_count, dim3(n_slices1), dim3(slice1 >= 1024 ? 1024u : threads), 0, st, scalars_all, fmt, plan, slice1, pb1, rb1, ctl + 4, run_off[0], cur,
-                         long_count + 1);
-      const size_t part_lds = (size_t)3 * (1u << pb1) * 4 + (size_t)cap * 8;
-      hipLaunchKernelGGL((msm_part_scatter<false, false>), dim3(n_slices), dim3(threads), part_lds, st, scalars_all, fmt, plan, slice, pb1, rb1, 0u, cap, cur, keys[1],
-                         vals[1]);
-    }
-    uint32_t runs = 1u << pb1, side = 1;
-    if (lv[1]) {                    // the second level: msm_radix_count / _scatter cut each run of level 1 by the next lv[1] bits
-      const uint32_t bits = lv[1], nd = 1u << bits, n_sub = runs * nd, shift = rb1 - bits;
-      uint64_t per_run = max_entries / runs;
-      uint32_t gx = (uint32_t)((per_run + RADIX_SLICE - 1) / RADIX_SLICE) + (runs > 1 ? 1 : 0);
-      if (gx > 4096) gx = 4096;
-      const uint32_t t = (n_sub + SCAN_TILE - 1) / SCAN_TILE;
-      BP_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)n_sub * 4, st));
-      hipLaunchKernelGGL(msm_radix_count, dim3(gx, runs), dim3(1024), 0, st, keys[side], run_off[0], shift, bits, cnt);
-      hipLaunchKernelGGL(scan_tile_sums, dim3(t), dim3(256), 0, st, cnt, n_sub, tile_sums);
-      hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(256), 0, st, tile_sums, t, run_off[1] + n_sub);
-      hipLaunchKernelGGL(scan_apply, dim3(t), dim3(256), 0, st, cnt, n_sub, tile_sums, run_off[1], cur);
-      hipLaunchKernelGGL(msm_radix_scatter, dim3(gx, runs), dim3(1024), RADIX_SLICE * 9, st, keys[side], vals[side], run_off[0], shift, bits,
-                         cur, keys[side ^ 1], vals[side ^ 1]);
+  BP_HIP(ctx, hipMemsetAsync(b.ctl, 0, (size_t)hp.ctl_zeroed * 4, st));
+  if (hp.sort == 2) {
+    level1_launch(st, hp, scalars_all, fmt, b, b.run_off, b.keys[0], b.vals[0]);
+    (hp.packed ? final_runs_launch<true> : final_runs_launch<false>)(st, hp, b, b.keys[0], b.vals[0], b.run_off);
+  } else {
+    uint32_t* const run_off[2] = {b.run_off + 4,                     // after level 1: 2^lv[0] + 1 entries
+                                  b.run_off + 8 + hp.n_final};       // after level 2: n_final + 1 entries
+    level1_launch(st, hp, scalars_all, fmt, b, run_off[0], b.keys[1], b.vals[1]);
+    uint32_t side = 1;
+    if (hp.lv[1]) {                 // the second level: msm_radix_count / _scatter cut each run of level 1 by the next lv[1] bits
+      const dim3 grid(hp.gx2, 1u << hp.lv[0]);
+      BP_HIP(ctx, hipMemsetAsync(b.run_cnt, 0, (size_t)hp.n_sub * 4, st));
+      hipLaunchKernelGGL(msm_radix_count, grid, dim3(1024), 0, st, b.keys[side], run_off[0], hp.shift2, hp.lv[1], b.run_cnt);
+      hipLaunchKernelGGL(scan_tile_sums, dim3(hp.scan_tiles), dim3(256), 0, st, b.run_cnt, hp.n_sub, b.tile_sums);
+      hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(256), 0, st, b.tile_sums, hp.scan_tiles, run_off[1] + hp.n_sub);
+      hipLaunchKernelGGL(scan_apply, dim3(hp.scan_tiles), dim3(256), 0, st, b.run_cnt, hp.n_sub, b.tile_sums, run_off[1], b.run_cur);
+      hipLaunchKernelGGL(msm_radix_scatter, grid, dim3(1024), RADIX_SLICE * 9, st, b.keys[side], b.vals[side], run_off[0], hp.shift2, hp.lv[1], b.run_cur,
+                         b.keys[side ^ 1], b.vals[side ^ 1]);
       side ^= 1;
-      runs = n_sub;
     }
-    uint32_t* const final_off = run_off[lv[1] ? 1 : 0];
-    const RunRecords<false> rr{keys[side], vals[side], (1u << rbits) - 1u, 0u};
-    hipLaunchKernelGGL(msm_radix_final<false>, dim3(runs < 4096 ? runs : 4096), dim3(1024), rhist, st, rr, final_off, runs, rbits, total, offsets,
-                       sorted, rlong_n, rlong_list, counts);
-    if (runs > 1) {                 // long runs (none for uniformly random scalars beyond the top window's): slice-parallel
-      const dim3 lgrid(256, runs < 16 ? runs : 16);
-      hipLaunchKernelGGL(msm_radix_long_count<false>, lgrid, dim3(1024), rhist, st, rr, final_off, runs, rbits, total, rlong_n, rlong_list, counts,
-                         offsets, cursors, run_ticket);
-      hipLaunchKernelGGL(msm_radix_long_scatter<false>, lgrid, dim3(1024), rhist, st, rr, final_off, rbits, rlong_n, rlong_list, cursors, sorted);
-    }
+    final_runs_launch<false>(st, hp, b, b.keys[side], b.vals[side], run_off[hp.lv[1] ? 1 : 0]);
   }
   BP_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  const dim3 acc_grid((unsigned)((n_chunks + 255) / 256));
-  hipLaunchKernelGGL(msm_accumulate<2>, acc_grid, dim3(256), 0, st, d_points28, sorted, offsets, plan, bucket_sum, partial);
+  hipLaunchKernelGGL(msm_accumulate<2>, dim3(hp.acc_grid), dim3(256), 0, st, d_points28, b.sorted, offsets, plan, bucket_sum, partial);
   BP_HIP(ctx, hipEventRecord(ctx->ev[2], st));
-  // fix-up of the buckets cut by chunk edges.  Long buckets (tables at c <= 17: every one of the 2^15 buckets spans several chunks):
-  // two lanes per bucket = one wave per SIMD, half the chain.  Short buckets (wide windows, per-window bucket sets): most buckets
-  // sit inside one chunk -- one lane per chunk edge.  BP_MSM_FIXUP=1 / 2 forces the per-bucket / per-edge form.
-  const uint32_t fixup_env = knob_u32("BP_MSM_FIXUP", 0, 0, 2);
-  const bool by_edges = fixup_env ? fixup_env == 2 : max_entries / total < 2ull * plan.chunk;
-  path[9] = by_edges;
-  if (by_edges)
-    hipLaunchKernelGGL(msm_fixup_edges, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count,
-                       long_list, long_cap);
+  if (hp.by_edges)
+    hipLaunchKernelGGL(msm_fixup_edges, dim3(hp.fixup_grid), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count, long_list, hp.long_cap);
   else if (table_c)
-    hipLaunchKernelGGL(msm_fixup<2>, dim3((unsigned)(((uint64_t)total * 2 + 255) / 256)), dim3(256), 0, st, offsets, plan, bucket_sum, partial,
-                       long_count, long_list, long_cap);
+    hipLaunchKernelGGL(msm_fixup<2>, dim3(hp.fixup_grid), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count, long_list, hp.long_cap);
   else
-    hipLaunchKernelGGL(msm_fixup<1>, dim3((total + 255) / 256), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count, long_list,
-                       long_cap);
-  hipLaunchKernelGGL(msm_fixup_long, dim3(512), dim3(256), 256 * sizeof(proj28_slot), st, offsets, plan, bucket_sum, partial,
-                     long_count, long_list, long_cap, long_scratch, long_ticket);
-  // The tree over the `total` leaves (tables: B = 2^(c-1) buckets, J B for a batch; table-free: the forest of W trees, W B leaves),
-  // level by level.  A level with at least PLANES_WIDE_MIN additions is throughput bound: one addition per lane through HBM
-  // (msm_planes_level01 / msm_planes_level: six such levels at 2^19 leaves, seven for the table-free forest of 16 x 2^15).  The rest
-  // is latency bound: up to PLANES_STEP_LOG levels per launch inside workgroups, cooperative additions (msm_planes_step).
-  // A node of 2^k buckets carries k + 1 values; the two ping-pong buffers hold at most B values (level 1).
-  const uint32_t levels = plan.c - 1;               // >= 1 (make_plan keeps c >= 2)
-  const uint64_t wide_min = knob_u32("BP_MSM_PLANES_WIDE_MIN", 24000, 256, 1u << 30);
-  uint32_t k = 0, nodes = total, n_wide = 0;            // total = J B leaves: a forest of J trees (J > 1: the vectors of a batch)
-  while (n_wide < levels && (uint64_t)(total >> (n_wide + 1)) * (n_wide + 1) >= wide_min) n_wide++;
-  if (n_wide == levels) n_wide = levels - 1;            // the last level is always a step: it writes the result where the epilogue reads it
-  // levels 0 and 1 have the same number of additions, so a wide level 0 comes with a wide level 1 and the two run fused (msm_planes_level01);
-  // a lone wide leaf level (two-level trees, c = 3: knobs only) takes the step path
-  if (n_wide < 2) n_wide = 0;
-  path[10] = n_wide;
-  proj28_slot* tmp[2] = {nullptr, nullptr};
-  {
-    size_t need[2] = {0, 0};
-    uint32_t kk = 0, flip = 0;
-    while (kk < levels) {
-      const uint32_t m = kk < n_wide ? 1 : (levels - kk < PLANES_STEP_LOG ? levels - kk : PLANES_STEP_LOG);
-      kk += m;
-      if (kk < levels) {
-        const size_t slots = (size_t)(total >> kk) * (kk + 1);
-        if (slots > need[flip]) need[flip] = slots;
-      }
-      flip ^= 1;
-    }
-    if (need[0]) BP_TRY(ws_get(ctx, "msm.planes_tmp0", need[0] * sizeof(proj28_slot), (void**)&tmp[0]));
-    if (need[1]) BP_TRY(ws_get(ctx, "msm.planes_tmp1", need[1] * sizeof(proj28_slot), (void**)&tmp[1]));
-  }
+    hipLaunchKernelGGL(msm_fixup<1>, dim3(hp.fixup_grid), dim3(256), 0, st, offsets, plan, bucket_sum, partial, long_count, long_list, hp.long_cap);
+  hipLaunchKernelGGL(msm_fixup_long, dim3(512), dim3(256), 256 * sizeof(proj28_slot), st, offsets, plan, bucket_sum, partial, long_count, long_list, hp.long_cap,
+                     long_scratch, long_ticket);
+  // the bucket tree, launch by launch; the last one writes where the epilogue reads (tables: the window sums and the status word behind them)
+  uint32_t* const status_out = reinterpret_cast<uint32_t*>(window_sum + n_planes);
   const proj28_slot* in = bucket_sum;
-  int flip = 0;
-  while (k < levels) {
-    const bool leaf = k == 0;
-    if (leaf && n_wide) {                 // levels 0 and 1 in one launch, four buckets per lane
-      nodes >>= 2;
-      flip ^= 1;                          // the output takes the buffer level 1 would have taken
-      hipLaunchKernelGGL(msm_planes_level01, dim3((nodes + 255) / 256), dim3(256), 0, st, offsets, in, nodes, tmp[flip]);
-      in = tmp[flip];
-      k = 2;
-    } else if (k < n_wide) {
-      nodes >>= 1;
-      const uint64_t items = (uint64_t)nodes * (k + 1);
-      const dim3 grid((unsigned)((items + 255) / 256));
-      hipLaunchKernelGGL(msm_planes_level, grid, dim3(256), 0, st, offsets, in, k, nodes, tmp[flip]);
-      in = tmp[flip];
-      k += 1;
+  for (uint32_t i = 0; i < hp.n_steps; i++) {
+    const MsmTreeStep& s = hp.step[i];
+    const bool last = s.out == MSM_OUT_FINAL;
+    proj28_slot* out_nodes = last ? (table_c ? window_sum : roots) : tmp[s.out];
+    const dim3 grid(s.gx, s.gy);
+    if (s.kind == MSM_STEP_LEVEL01) {
+      hipLaunchKernelGGL(msm_planes_level01, grid, dim3(256), 0, st, offsets, in, s.nodes, out_nodes);
+    } else if (s.kind == MSM_STEP_LEVEL) {
+      hipLaunchKernelGGL(msm_planes_level, grid, dim3(256), 0, st, offsets, in, s.k, s.nodes, out_nodes);
     } else {
-      const uint32_t m = levels - k < PLANES_STEP_LOG ? levels - k : PLANES_STEP_LOG;
-      nodes >>= m;
-      const bool last = k + m == levels;
-      proj28_slot* out_nodes = last ? (table_c ? window_sum : roots) : tmp[flip];
-      uint32_t* status_out = last && table_c ? reinterpret_cast<uint32_t*>(window_sum + n_planes) : (uint32_t*)nullptr;
-      const dim3 grid(nodes, k + 1);
-      const size_t lds = ((size_t)2 << m) * sizeof(proj28_slot);
-      if (leaf) hipLaunchKernelGGL(msm_planes_step<true>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
-      else hipLaunchKernelGGL(msm_planes_step<false>, grid, dim3(256), lds, st, offsets, in, k, m, out_nodes, long_count + 1, offsets + total, status_out);
-      in = out_nodes;
-      k += m;
+      uint32_t* so = last && table_c ? status_out : (uint32_t*)nullptr;
+      if (s.k == 0) hipLaunchKernelGGL(msm_planes_step<true>, grid, dim3(256), s.lds, st, offsets, in, s.k, s.m, out_nodes, status, offsets + total, so);
+      else hipLaunchKernelGGL(msm_planes_step<false>, grid, dim3(256), s.lds, st, offsets, in, s.k, s.m, out_nodes, status, offsets + total, so);
     }
-    flip ^= 1;
+    in = out_nodes;
   }
   if (!table_c)           // W roots of c values each -> W x quads partial Horner values (the host finishes what msm.rs:42-46, 107-115 compute)
-    hipLaunchKernelGGL(msm_planes_window_quads, dim3(W), dim3(64), 0, st, roots, plan.c, quads, window_sum, long_count + 1, offsets + total,
-                       reinterpret_cast<uint32_t*>(window_sum + n_planes));
+    hipLaunchKernelGGL(msm_planes_window_quads, dim3(plan.W), dim3(64), 0, st, roots, plan.c, hp.quads, window_sum, status, offsets + total, status_out);
   BP_HIP(ctx, hipGetLastError());
   if (d_blob) {
     MsmBlobHeader hdr;
     memset(&hdr, 0, sizeof hdr);
     hdr.magic = MSM_BLOB_MAGIC;
     hdr.c = plan.c;
-    hdr.Wr = table_c ? 1 : Wr;
+    hdr.Wr = table_c ? 1 : hp.Wr;
     hdr.n_planes = n_planes;
     hdr.tables = table_c != 0;
-    hdr.quads = table_c ? 0u : quads;
+    hdr.quads = table_c ? 0u : hp.quads;
     hipLaunchKernelGGL(msm_write_blob, dim3(1), dim3(256), 0, st, window_sum, hdr, (uint8_t*)d_blob);
     BP_HIP(ctx, hipGetLastError());
   } else {
@@ -542,12 +260,12 @@ int msm_launch_many(bp_ctx* ctx, const g1_affine28* d_points28, uint32_t J, cons
   out->empty = false;
   out->tables = table_c != 0;
   out->c = plan.c;
-  out->Wr = table_c ? 1 : Wr;
+  out->Wr = table_c ? 1 : hp.Wr;
   out->n_planes = n_planes;
-  out->quads = quads;
-  out->adds = max_entries;      // upper bound (blob mode keeps it); msm_finish replaces it by the exact count of non-zero digits
+  out->quads = hp.quads;
+  out->adds = hp.entries;       // upper bound (blob mode keeps it); msm_finish replaces it by the exact count of non-zero digits
   out->h_windows = h_windows;
-  memcpy(ctx->msm_path, path, sizeof path);
+  msm_plan_path(hp, ctx->msm_path);      // what this launch decided (bp_msm_last_path): host words only, set once everything is enqueued
   return BP_OK;
 }
 

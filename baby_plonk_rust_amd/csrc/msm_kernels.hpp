@@ -33,53 +33,10 @@
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "msm_digits.hpp"
+#include "msm_plan.hpp"      // the limits, MsmPlan
 
 namespace bp {
 
-constexpr int MSM_MAX_C = 16;            // per-window bucket sets (any point set): one LDS histogram per window
-constexpr int MSM_MAX_TABLE_C = 24;      // fixed-base tables: partitioned counting sort above 16 bits
-constexpr uint32_t MSM_HIST_LOG = 15;    // buckets per LDS histogram (128 KiB of the 160)
-constexpr int MSM_MAX_WINDOWS = 128;
-
-struct MsmPlan {
-  uint32_t n;          // number of (point, scalar) pairs
-  uint32_t c;          // window bits
-  uint32_t W;          // windows
-  uint32_t B;          // buckets per window = 2^(c-1)
-  uint32_t chunk;      // entries per lane in msm_accumulate when every digit is non-zero (sizes the lane count and the partial slots)
-  uint32_t lanes;      // 0: the chunk is fixed (BP_MSM_CHUNK).  Else the lanes of msm_accumulate = ceil(W n / chunk): the kernels cut
-                       // the sorted list into ceil(M / lanes) entries per lane from the ACTUAL entry count M (zero digits are
-                       // not entries: small or sparse scalars keep every lane busy with short chains instead of a few lanes with long ones)
-  uint32_t bias[9];    // sum_{w < W-1} 2^(c-1) * 2^(c*w)   (the top window is unsigned)
-  // Two bucket layouts share every kernel.  Per-window buckets (any point set): window w owns buckets
-  // [w B, (w+1) B) and an entry is the point index i.  Fixed-base tables (bp_srs_precompute): the SRS carries
-  // T[w][i] = 2^(cw) P_i, every window feeds the SAME B buckets and an entry is the table index w * stride + i,
-  // so the reduction and the Horner epilogue run over one window instead of W.
-  uint32_t total;      // number of buckets: W * B, or B with tables
-  uint32_t wbuckets;   // bucket-index stride per window: B, or 0 with tables
-  uint32_t wpoints;    // point-index stride per window: 0, or the table row length with tables
-  // Windows wider than 16 bits (fixed-base tables only): one window's 2^(c-1) buckets no longer fit one LDS histogram
-  // (parts > 1); those MSMs take the partitioned (radix) bucket sort, section 4c.
-  uint32_t parts;      // 1, or B >> 15
-  // Several scalar vectors against ONE table set in one pipeline (the commitments of a prover round, prover.rs:249-251,
-  // 483-485, 640-641): vector j owns the buckets [j B, (j + 1) B), so the sort, the accumulation, the fix-up and the tree run
-  // once over J bucket sets and deliver J results.  n is then the longest vector; scalar (j, i) is element j * n + i of the
-  // pipeline's index space, elements with i >= nj[j] do not exist.  Partition sort only (msm_part_*); J = 1 everywhere else.
-  uint32_t J;          // 1 .. MSM_MAX_BATCH
-  uint32_t nj[4];      // length of vector j
-  // Fixed-base tables free the digit radix from being a power of two (round 6): T[w][i] = R^w P_i for ANY R.  W windows of c bits cover
-  // c W >= 256 bits, but a scalar has 255: at c = 20 (13 windows) five bits of every bucket index are bought and never used.  With
-  // R = the smallest (low Hamming weight) even number whose W-th power exceeds 2^256 the signed digits |d| <= R / 2 fill R / 2 buckets
-  // instead of 2^(c-1): 425 984 instead of 524 288 at 13 windows, 1 327 104 instead of 2 097 152 at 12 -- a fifth to a third of the
-  // bucket tree's leaves (and of its additions) gone; the live buckets are a PREFIX of the 2^(c-1) the tree is sized for, the rest
-  // stay empty and whole waves of the tree skip them.  radix = 0: power-of-two windows (every table-free MSM; widths that waste < 10 %).
-  // Digits: k' = k + bias (bias = sum_{w < W-1} (R / 2) R^w), f = k' / R^W as a 288-bit fraction = the top limbs of k' * radix_m
-  // (radix_m = ceil(2^512 / R^W)) + 2 ulp, then W times "multiply by R, take the integer part" from the top digit down; signed digit
-  // = that - R / 2 below the top window.  Exact: the fraction's error is in [0, 2^-257 + 2^-287) and 1 / R^W > 2^-256.93 (make_plan).
-  uint32_t radix;
-  uint32_t radix_m[8];
-};
-constexpr uint32_t MSM_MAX_BATCH = 4;
 struct MsmScalars { const fr_t* p[MSM_MAX_BATCH]; };
 
 // bucket index inside a window for a non-zero digit: |d| - 1 in [0, 2^(c-1))
@@ -90,7 +47,7 @@ extern __shared__ uint32_t msm_lds_hist[];        // one run's bucket histogram 
 // ---------------------------------------------------------------- 3. scan (three small launches)
 // offsets[0..total] = exclusive prefix sums of counts[0..total); cursors = copy of offsets[0..total).
 // Tile = 4096 counts per workgroup (256 lanes x 16).  scan_tile_sums -> scan_block_sums -> scan_apply.
-constexpr uint32_t SCAN_TILE = 4096, SCAN_PER_LANE = 16;
+constexpr uint32_t SCAN_PER_LANE = 16;      // SCAN_TILE = 256 lanes x 16
 
 __device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t* lds, uint32_t& block_total) {
   // wave-level inclusive scan by shuffles, then a 4-entry LDS hop across the waves of the workgroup
@@ -192,7 +149,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32
 //   msm_radix_final     one workgroup per final run: histogram of its 2^rbits buckets, prefix = the buckets' offsets (written
 //                       to `offsets` directly: no global count / scan over buckets), then the entries in bucket order
 // One or two partition levels of <= 8 bits each; the record arrays ping-pong.
-constexpr uint32_t RADIX_SLICE = 8192, RADIX_PER_LANE = RADIX_SLICE / 1024, RADIX_MAX_DIGITS = 256;
+constexpr uint32_t RADIX_PER_LANE = RADIX_SLICE / 1024, RADIX_MAX_DIGITS = 256;
 
 // run r = records [run_off[r], run_off[r + 1]); the workgroups blockIdx.x, blockIdx.x + gridDim.x, ... take its slices
 __global__ void __launch_bounds__(1024) msm_radix_count(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ run_off, uint32_t shift,
@@ -429,7 +386,6 @@ __global__ void __launch_bounds__(1024) msm_radix_long_scatter(RunRecords<PACKED
 //                      partition's share lane-adjacent
 //   msm_radix_final    one workgroup per final run, as in 4c (packed records where they fit: RunRecords)
 // No digit array, no record arrays before the final runs, no scan launches.
-constexpr uint32_t PART_MAX_BITS = 12, PART_MAX = 1u << PART_MAX_BITS;
 
 // every (bucket id, entry | sign << 31) of scalar i with a non-zero digit, in window order.  status != null: canonical-bytes inputs are
 // range-checked (Scalar::from_bytes rejects values >= q, scalar.rs:264-288)
@@ -945,7 +901,6 @@ __global__ void __launch_bounds__(64) msm_blob_sum(const uint8_t* __restrict__ b
 // Buckets that straddle chunk edges: add their partials.  Short chains (the common case: 2-3 partials) are
 // summed by one lane; a bucket cut into more than FIXUP_LONG chunks (skewed scalars, the narrow top window)
 // is queued for msm_fixup_long, where a whole workgroup strides over its partials and tree-reduces in LDS.
-constexpr uint32_t FIXUP_LONG = 16;
 
 __device__ __forceinline__ uint32_t partial_slot(uint32_t bucket_start, uint32_t t, uint32_t chunk) {
   return bucket_start <= t * chunk ? 0u : 1u;     // slot 0 = run that begins at the chunk start, 1 = run that ends at its end
@@ -1045,7 +1000,6 @@ __device__ __forceinline__ g1_proj28 block_tree_sum28(g1_proj28 v, uint32_t live
 // workgroups, one slice of its partials each, into `scratch`; the workgroup whose slice is finished last (a ticket per
 // queued bucket, zero before the launch and zero again after it) adds the slice sums.
 // An empty queue (the normal case: uniformly random scalars on a table) costs one launch of workgroups that read one word and leave.
-constexpr uint32_t FIXUP_LONG_SLICES = 8, FIXUP_LONG_SPLIT_FROM = 2048;
 __global__ void __launch_bounds__(256, 2)
 msm_fixup_long(const uint32_t* __restrict__ offsets, MsmPlan plan, proj28_slot* __restrict__ bucket_sum,
                const proj28_slot* __restrict__ partial, const uint32_t* __restrict__ long_count,
@@ -1231,7 +1185,6 @@ msm_planes_level01(const uint32_t* __restrict__ offsets, const proj28_slot* __re
 // LEAF: k = 0, the input nodes are the bucket sums (empty buckets read as the identity).
 // status_out != null on the last step only: the scalar-status word and the entry count ride to the host behind the sums.
 // LDS: two arrays of 2^m slots.   out[w * (k + m + 1) + {0: A, 1 + j: T_j}]
-constexpr uint32_t PLANES_STEP_LOG = 6;
 template <bool LEAF>
 __global__ void __launch_bounds__(256, 2)
 msm_planes_step(const uint32_t* __restrict__ offsets, const proj28_slot* __restrict__ in, uint32_t k, uint32_t m,

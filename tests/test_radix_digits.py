@@ -30,7 +30,7 @@ def hc():
 
 
 def windows_of(c):
-    """W as make_plan (msm.hip) finds it for power-of-two windows: ceil(255 / c), one more while the unsigned top window cannot hold
+    """W as msm_width_compute (msm_plan.hpp) finds it for power-of-two windows: ceil(255 / c), one more while the unsigned top window cannot hold
     the largest scalar's top digit plus the carry of the signed ones below"""
     W = max(2, (255 + c - 1) // c)
     while True:
@@ -64,7 +64,7 @@ def test_radix_choice_per_width(hc):
         assert bias == sum((R // 2) * R ** w for w in range(W - 1))
         # the largest scalar keeps its (unsigned) top digit inside the live buckets
         assert (Q - 1 + bias) // R ** (W - 1) <= R // 2
-    # (msm_radix_compute answers for every width; the library's make_plan takes the radix from 21 bits only -- at 20 bits the 2^19-bucket
+    # (msm_radix_compute answers for every width; the library's msm_table_radix takes the radix from 21 bits only -- at 20 bits the 2^19-bucket
     # tree runs every wide level in one wave round and gains nothing from fewer live buckets, profiles/r06_tail_ab.txt)
     # the widths that waste the most bucket range: 20 bits (thirteen windows), 22 (twelve)
     assert used[20] == (13, 0xD0000) and used[20][1] // 2 == 425984       # against 524 288 buckets at 2^19

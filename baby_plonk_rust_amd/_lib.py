@@ -91,6 +91,11 @@ SIGNATURES = {
     "bp_circuit_free": (_int, [_vp, _u64]),
     "bp_circuit_commitments": (_int, [_vp, _u64, _u64, _vp]),
     "bp_make_s_polynomials": (_int, [_u32, _vp, _vp, _vp, _vp]),
+    "bp_circuit_load_wires": (_int, [_vp, _u32, _vp, _vp, _sz, _int, _int, _pp(_u64)]),
+    "bp_circuit_load_wires_last_stats": (_int, [_vp, _vp]),
+    "bp_circuit_export_columns": (_int, [_vp, _u64, _int, _vp]),
+    "bp_circuit_assign_device": (_int, [_vp, _u64, _vp, _sz, _int, _int, _vp, _vp, _vp, _vp]),
+    "bp_prove_assignment": (_int, [_vp, _u64, _u64, _vp, _sz, _int, _int, _vp, _vp]),
     "bp_prove": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "bp_prove_last_stats": (_int, [_vp, _vp, _pp(C.c_float)]),
     "bp_circuit_check_sigma": (_int, [_vp, _u64, _vp]),

@@ -1205,6 +1205,73 @@ class Circuit:
         self.ctx.check(self.ctx._lib.bp_circuit_load(self.ctx._h, n.bit_length() - 1, ptrs, FR_MONT, 0, C.byref(h)), "bp_circuit_load")
         self.handle = h.value
 
+    @classmethod
+    def from_wires(cls, selectors, wire_ids, n_public=0, ctx=None, fmt=FR_MONT):
+        """bp_circuit_load_wires: the circuit from what follows the reference's parser.  selectors: QL QR QM QO QC (a dict by column name
+        or five arrays; fmt=FR_BYTES_LE: [n, 32] uint8 canonical bytes); wire_ids: [n, 3] uint32 as make_s_polynomials takes them; rows
+        0 .. n_public-1 are the public rows.  S1 S2 S3 are built on the GPU.  Selectors given as torch CUDA tensors (int64 [n, 4]) go with
+        wire_ids as a CUDA int32 tensor: everything is read in place."""
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context()
+        sel = [selectors[k] for k in CIRCUIT_COLUMNS[:5]] if isinstance(selectors, dict) else list(selectors)
+        on_device = hasattr(wire_ids, "data_ptr")
+        if on_device:
+            if len(sel) != 5 or not all(hasattr(s, "data_ptr") for s in sel):
+                raise BpError(-1, "Circuit.from_wires", "device wire ids go with five device selector columns")
+            n = wire_ids.shape[0]
+            ok = all(s.shape[0] == n for s in sel) and wire_ids.numel() == 3 * n and wire_ids.element_size() == 4
+            ptrs, ids_ptr, keep = [s.data_ptr() for s in sel], wire_ids.data_ptr(), (sel, wire_ids)
+        else:
+            sel = [_fr_array(s) if fmt == FR_MONT else np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 32) for s in sel]
+            ids = np.ascontiguousarray(wire_ids, dtype=np.uint32)
+            n = ids.shape[0]
+            ok = len(sel) == 5 and ids.ndim == 2 and ids.shape[1] == 3 and all(len(s) == n for s in sel)
+            ptrs, ids_ptr, keep = [s.ctypes.data for s in sel], ids.ctypes.data, (sel, ids)
+        if not ok or n < 8 or n & (n - 1):
+            raise BpError(-2, "Circuit.from_wires", "five selector columns and [n, 3] wire ids of one power-of-two length >= 8 expected")
+        self.group_order, self.n_public = n, n_public
+        h = C.c_uint64()
+        self.ctx.check(self.ctx._lib.bp_circuit_load_wires(self.ctx._h, n.bit_length() - 1, (C.c_void_p * 5)(*ptrs), ids_ptr, n_public, fmt,
+                                                           int(on_device), C.byref(h)), "bp_circuit_load_wires")
+        del keep
+        self.handle = h.value
+        return self
+
+    def load_stats(self):
+        """HIP-event milliseconds of the last from_wires on this context, by stage"""
+        ms = (C.c_float * 5)()
+        self.ctx.check(self.ctx._lib.bp_circuit_load_wires_last_stats(self.ctx._h, ms), "bp_circuit_load_wires_last_stats")
+        return dict(zip(("upload_ms", "max_id_ms", "sort_ms", "link_ms", "build_ms"), ms))
+
+    def columns(self, fmt=FR_MONT, names=CIRCUIT_COLUMNS):
+        """bp_circuit_export_columns: {column name: [n, 4] Montgomery limbs} of the handle's Lagrange columns (fmt=FR_BYTES_LE: [n, 32]
+        uint8); names: the columns wanted"""
+        n = self.group_order
+        out = {k: (np.zeros((n, 4), dtype=np.uint64) if fmt == FR_MONT else np.zeros((n, 32), dtype=np.uint8)) for k in names}
+        ptrs = (C.c_void_p * 8)(*[out[k].ctypes.data if k in out else None for k in CIRCUIT_COLUMNS])
+        self.ctx.check(self.ctx._lib.bp_circuit_export_columns(self.ctx._h, self.handle, fmt, ptrs), "bp_circuit_export_columns")
+        return out
+
+    def _values(self, values, fmt):
+        """a value array as the two assignment calls take it -> (pointer, count, on_device, what to keep alive)"""
+        if hasattr(values, "data_ptr"):
+            return values.data_ptr(), values.shape[0], 1, values
+        v = _fr_array(values) if fmt == FR_MONT else np.ascontiguousarray(values, dtype=np.uint8).reshape(-1, 32)
+        return v.ctypes.data, len(v), 0, v
+
+    def assign(self, values, fmt=FR_MONT, public_input=True):
+        """bp_circuit_assign_device: values[id] per variable ([m, 4] Montgomery limbs, fmt=FR_BYTES_LE: [m, 32] uint8, or a torch CUDA
+        tensor int64 [m, 4]) -> Assignment: the columns a, b, c and PI (None with public_input=False) as torch CUDA tensors int64 [n, 4]"""
+        import torch
+        n = self.group_order
+        t = [torch.empty((n, 4), dtype=torch.int64, device=torch.device("cuda", self.ctx.device)) for _ in range(4 if public_input else 3)]
+        torch.cuda.synchronize(self.ctx.device)
+        ptr, count, on_device, keep = self._values(values, fmt)
+        self.ctx.check(self.ctx._lib.bp_circuit_assign_device(self.ctx._h, self.handle, ptr, count, fmt, on_device, t[0].data_ptr(), t[1].data_ptr(),
+                                                              t[2].data_ptr(), t[3].data_ptr() if public_input else None), "bp_circuit_assign_device")
+        del keep
+        return Assignment(t[0], t[1], t[2], t[3] if public_input else None)
+
     def free(self):
         self.ctx.check(self.ctx._lib.bp_circuit_free(self.ctx._h, self.handle), "bp_circuit_free")
 
@@ -1254,6 +1321,19 @@ _ABSENT = 0xFFFFFFFFFFFFFFFF
 def _cell(v):
     """cell number 3 * row + col of the C ABI -> (col, row); None for an absent position"""
     return None if v == _ABSENT else (int(v) % 3, int(v) // 3)
+
+
+class Assignment(collections.namedtuple("Assignment", "a b c public_input")):
+    """what Circuit.assign returns: the witness columns in HBM (torch CUDA tensors, int64 [n, 4] Montgomery limbs); public_input may
+    be None.  Prover.check and Prover.prove_device take them where they are."""
+    __slots__ = ()
+
+    def pointers(self):
+        return [self.a.data_ptr(), self.b.data_ptr(), self.c.data_ptr(), None if self.public_input is None else self.public_input.data_ptr()]
+
+    def host(self):
+        """the columns as [n, 4] uint64 arrays on the host (public_input: None stays None)"""
+        return [None if t is None else t.cpu().numpy().view(np.uint64) for t in self]
 
 
 class SigmaReport(collections.namedtuple("SigmaReport", "bad_labels first_bad_label bad_indegree first_bad_indegree")):
@@ -1309,8 +1389,25 @@ class Prover:
                                   out.ctypes.data), "bp_prove")
         return bytes(out)
 
-    def check(self, a, b, c, public_input=None, fmt=FR_MONT):
-        """where would prove_with_blinding refuse this witness?  (Circuit.check_witness) -> WitnessReport"""
+    def prove_assignment(self, values, blinders, fmt=FR_MONT):
+        """bp_prove_assignment on a Circuit.from_wires circuit: values[id] per variable (as Circuit.assign takes them) -> the 624 bytes
+        prove_with_blinding returns for the expanded columns"""
+        bl = np.frombuffer(b"".join((int(v) % Q).to_bytes(32, "little") for v in blinders), dtype=np.uint8).copy()
+        if len(bl) != 352:
+            raise BpError(-2, "prove", "11 blinders expected")
+        ptr, count, on_device, keep = self.circuit._values(values, fmt)
+        out = np.zeros(624, dtype=np.uint8)
+        c_ = self.ctx
+        c_.check(c_._lib.bp_prove_assignment(c_._h, self.setup.handle, self.circuit.handle, ptr, count, fmt, on_device, bl.ctypes.data,
+                                             out.ctypes.data), "bp_prove_assignment")
+        del keep
+        return bytes(out)
+
+    def check(self, a, b=None, c=None, public_input=None, fmt=FR_MONT):
+        """where would prove_with_blinding refuse this witness?  (Circuit.check_witness) -> WitnessReport.  `a` alone may be what
+        Circuit.assign returned: the columns are read where they are, in HBM"""
+        if isinstance(a, Assignment):
+            return self.circuit.check_witness_device(*a.pointers())
         return self.circuit.check_witness(a, b, c, public_input, fmt)
 
     def last_stats(self):

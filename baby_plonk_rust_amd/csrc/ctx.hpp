@@ -94,6 +94,10 @@ struct CircuitEntry {
   // made by the first check of the circuit and kept; sigma_report: what bp_circuit_check_sigma said then
   uint32_t* sigma_target = nullptr;
   uint64_t sigma_report[4] = {0, 0, 0, 0};
+  // bp_circuit_load_wires only (nullptr after bp_circuit_load): the 3n variable ids as they were given, cell 3 * row + col, and the
+  // count of public rows -- what bp_circuit_assign_device / bp_prove_assignment gather a value array through
+  uint32_t* wire_ids = nullptr;
+  size_t n_public = 0;
 };
 
 struct MemberWorker;     // persistent host thread of one member of a group context (capi_ctx.hip)
@@ -180,6 +184,7 @@ struct bp_ctx {
   uint32_t msm_path[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float prove_ms[6] = {0, 0, 0, 0, 0, 0};            // host wall clock of rounds 1..5 and of the whole bp_prove
   float check_ms[3] = {0, 0, 0};                     // last bp_circuit_check_*: sigma decode (0: cached), upload + conversion, the check kernel
+  float wires_ms[5] = {0, 0, 0, 0, 0};               // last bp_circuit_load_wires: upload + conversion, largest id, sort, roots + link, derived forms
   bool msm_async_pending = false;  // bp_msm_g1_blob_device_async enqueued an MSM whose events have not been read yet
   float ntt_ms = 0;
   bool ntt_async_pending = false;  // bp_ntt_fr_device_async enqueued a transform whose events have not been read yet

@@ -130,6 +130,8 @@ void circuit_release(CircuitEntry& e) {
   }
   if (e.sigma_target) (void)hipFree(e.sigma_target);
   e.sigma_target = nullptr;
+  if (e.wire_ids) (void)hipFree(e.wire_ids);
+  e.wire_ids = nullptr;
   for (CosetShare& sh : e.split) {
     DeviceGuard guard(sh.member ? sh.member->device : 0);
     if (sh.member) (void)hipStreamSynchronize(sh.member->stream);

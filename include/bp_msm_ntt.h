@@ -407,6 +407,37 @@ int  bp_circuit_commitments(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_h
  * of zeros.  Cells of one variable form a cycle in row-major order and the NEXT cell of the cycle receives THIS cell's
  * label column * w^row, columns numbered 1 2 3 (program.rs:126-137).  s1 s2 s3: 2^log_n Montgomery scalars each, host. */
 int  bp_make_s_polynomials(uint32_t log_n, const uint32_t* wire_ids, void* s1, void* s2, void* s3);
+/* A circuit from what follows the reference's parser (assembly.rs, program.rs): per row five selector values and three variable
+ * ids.  selectors: QL QR QM QO QC, 2^log_n scalars each; wire_ids: as bp_make_s_polynomials takes them (3 * 2^log_n ids, row-major,
+ * columns L R O, 0 = empty wire, any uint32).  S1 S2 S3 are built on the GPU by the map of program.rs:76-147 -- a stable 8-bit
+ * radix sort of the cells by id (as many passes as the largest id needs, 0..4) and one link pass -- and are the columns
+ * bp_make_s_polynomials returns, byte for byte.  n_public <= 2^log_n: rows 0 .. n_public-1 are the public rows and the public
+ * variable of row i is its L wire (prover.rs:114-127).  inputs_on_device != 0: the five selector pointers and wire_ids are HBM
+ * addresses, the selectors Montgomery.  BP_ERR_BAD_SCALAR: a BP_FR_BYTES_LE selector >= q.  The handle is a circuit handle like
+ * bp_circuit_load's (bp_prove, bp_circuit_commitments, the checks, group contexts, bp_circuit_free); it also keeps the wire ids in
+ * HBM (12 bytes per row) for the two assignment calls below, and the cell map the link pass wrote, so bp_circuit_check_sigma /
+ * _witness never decode such a circuit (decode time 0, both counts 0 and both positions absent: the cycles are a permutation
+ * by construction). */
+int  bp_circuit_load_wires(bp_ctx* ctx, uint32_t log_n, const void* const selectors[5], const uint32_t* wire_ids, size_t n_public,
+                           int scalar_fmt, int inputs_on_device, uint64_t* circuit_handle);
+/* HIP-event milliseconds of the last bp_circuit_load_wires on this ctx: upload + conversion of the inputs, the largest id (with its
+ * read-back), the sort, the table of roots + the link pass, the derived forms every circuit handle holds (bp_circuit_load's work). */
+int  bp_circuit_load_wires_last_stats(bp_ctx* ctx, float stage_ms[5]);
+/* The eight Lagrange columns QL QR QM QO QC S1 S2 S3 of any circuit handle, 2^log_n scalars each, to host memory; a NULL entry of
+ * `columns` skips that column.  How a verifier-side host sees the sigma bp_circuit_load_wires built. */
+int  bp_circuit_export_columns(bp_ctx* ctx, uint64_t circuit_handle, int scalar_fmt, void* const columns[8]);
+/* A witness from one value per variable: values[id] for id < n_values (slot 0 is never read: an empty wire is zero; device values
+ * must be Montgomery).  Writes 2^log_n Montgomery scalars per column into caller-owned HBM: a[row] = values[wire_ids[3 row]],
+ * b and c likewise, PI[row] = -values[wire_ids[3 row]] for row < n_public and zero elsewhere (prover.rs:120-127); d_pi may be NULL.
+ * Copy constraints hold by construction.  BP_ERR_LENGTH: a wire id >= n_values (bp_last_error names the lowest such cell; the
+ * columns are unspecified then); BP_ERR_BAD_SCALAR: a BP_FR_BYTES_LE value >= q; BP_ERR_INVALID_ARG: a handle of bp_circuit_load,
+ * which holds no wire ids.  Blocking. */
+int  bp_circuit_assign_device(bp_ctx* ctx, uint64_t circuit_handle, const void* values, size_t n_values, int scalar_fmt,
+                              int values_on_device, void* d_a, void* d_b, void* d_c, void* d_pi);
+/* bp_prove from the same value array: the gather of bp_circuit_assign_device into the prover's own workspace, then the proof.
+ * Same bytes and same errors as bp_prove on the expanded columns. */
+int  bp_prove_assignment(bp_ctx* ctx, uint64_t srs_handle, uint64_t circuit_handle, const void* values, size_t n_values,
+                         int scalar_fmt, int values_on_device, const uint8_t blinders[352], uint8_t proof[624]);
 /* One proof.  a, b, c: the witness as the three Lagrange wire columns the reference builds at prover.rs:186-227;
  * public_input: the Lagrange column of prover.rs:114-127 (-x_i in the first rows, zero elsewhere), NULL = all zero;
  * 2^log_n scalars each.  blinders: b1..b11 of prover.rs:110 as 11 x 32 canonical little-endian bytes -- an input here

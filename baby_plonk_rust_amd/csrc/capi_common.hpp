@@ -3,6 +3,7 @@
 #include <functional>
 #include <vector>
 
+#include "commit_plan.hpp"      // shard_range, shard_cut, shard_slice: which points and scalars lie on which shard
 #include "ctx.hpp"
 #include "host_codec.hpp"
 
@@ -39,7 +40,6 @@ int upload_fr(bp_ctx* ctx, const char* name, const void* host, size_t n, size_t 
 int download_fr(bp_ctx* ctx, bp::fr_t* d, void* host, size_t n, int fmt, const uint32_t* d_bad = nullptr);
 // work(r) for every member r for which use(r) holds: member 0 on the calling thread, the others on their own threads, all at once
 void over_members(bp_ctx* ctx, size_t R, const std::function<bool(size_t)>& use, const std::function<void(size_t)>& work);
-void shard_range(size_t n, size_t r, size_t R, size_t* lo, size_t* hi);
 std::vector<bp_ctx*> shards_of(bp_ctx* ctx);
 int ctx_create(bp_ctx** out, int device_id);
 // capi_srs.hip

@@ -182,12 +182,6 @@ void over_members(bp_ctx* ctx, size_t R, const std::function<bool(size_t)>& use,
   if (R > 0 && use(0)) work(0);
   for (size_t r : sent) lead->workers[r - 1]->wait();
 }
-// contiguous point range [lo, hi) of shard r of R over n points; the first n % R shards get one extra point
-void shard_range(size_t n, size_t r, size_t R, size_t* lo, size_t* hi) {
-  const size_t base = n / R, extra = n % R;
-  *lo = r * base + std::min(r, extra);
-  *hi = *lo + base + (r < extra ? 1 : 0);
-}
 // the single-device contexts an entry point has to visit: the members of a group, or the context itself
 std::vector<bp_ctx*> shards_of(bp_ctx* ctx) {
   if (is_group(ctx)) return ctx->members;

@@ -13,117 +13,140 @@
 
 using namespace bp;
 
+namespace bp {
+// the launch-and-finish rule of ctx.hpp
+int msm_finish_all(bp_ctx* ctx, MsmFlight* f, size_t count, int rc) {
+  const std::string launch_error = rc != BP_OK ? ctx->last_error : std::string();
+  auto launched = [&](size_t i) { return f[i].launched; };
+  auto finish = [&](size_t i) {
+    DeviceGuard guard(f[i].on->device);
+    f[i].rc = msm_finish(f[i].on, f[i].pend, f[i].out);
+  };
+  // In a group the waits and the host epilogues (window sums -> Horner, ~0.1 ms each) run on the members' own threads: eight in
+  // sequence would cost more than the shards' GPU time of a 2^20-point MSM split eight ways.
+  bool by_member = is_group(ctx) && count == ctx->members.size();
+  for (size_t r = 0; r < count && by_member; r++) by_member = f[r].on == ctx->members[r];
+  if (by_member) {
+    over_members(ctx, count, launched, finish);
+  } else {
+    for (size_t i = 0; i < count; i++)
+      if (launched(i)) finish(i);
+  }
+  if (rc != BP_OK) {
+    ctx->last_error = launch_error;
+    return rc;
+  }
+  for (size_t i = 0; i < count; i++)
+    if (launched(i) && f[i].rc != BP_OK) return lift(ctx, f[i].on, f[i].rc);
+  return BP_OK;
+}
+}  // namespace bp
+
+// Member m's slices of vectors that live in the HBM of the leader's device: once the leader's stream has reached `ready`, slice j
+// (len[j] scalars from src[j]) is copied GPU to GPU into the member's workspace, the slices back to back; at[j] = where it lies there.
+static int slices_from_leader(bp_ctx* m, int leader_device, hipEvent_t ready, int cnt, const fr_t* const* src, const size_t* len, const fr_t** at) {
+  size_t total = 0;
+  for (int j = 0; j < cnt; j++) total += len[j];
+  fr_t* d;
+  BP_TRY(ws_get(m, "io.scalars", total * sizeof(fr_t), (void**)&d));
+  BP_HIP(m, hipStreamWaitEvent(m->stream, ready, 0));
+  for (int j = 0; j < cnt; d += len[j++]) {
+    at[j] = d;
+    if (!len[j]) continue;
+    if (!peer_path(m, leader_device)) BP_HIP(m, hipMemcpyAsync(d, src[j], len[j] * sizeof(fr_t), hipMemcpyDeviceToDevice, m->stream));
+    else BP_HIP(m, hipMemcpyPeerAsync(d, m->device, src[j], leader_device, len[j] * sizeof(fr_t), m->stream));
+  }
+  return BP_OK;
+}
+
 // Enqueue the MSM of one shard: scalars[0..n) against the member's points [local_first, local_first + n).
-//   where 0: `scalars` is host memory; 1: HBM of this member's device; 2: HBM of device src_device (the leader's): copied
-//   GPU to GPU into the member's workspace once the leader's stream has reached `ready`.
+//   where 0: `scalars` is host memory; 1: HBM of this member's device; 2: HBM of device src_device (the leader's), behind `ready`
 static int msm_shard_launch(bp_ctx* m, SrsEntry* e, size_t local_first, const void* scalars, size_t n, int fmt, int where, int src_device,
                             hipEvent_t ready, int slot, void* d_blob, MsmPending* pend) {
   DeviceGuard guard(m->device);
-  const fr_t* d_scalars = (const fr_t*)scalars;
-  if (where != 1 && n) {
+  const fr_t *d_scalars = (const fr_t*)scalars, *src = d_scalars;
+  if (where == 0 && n) {
     fr_t* d;
     BP_TRY(ws_get(m, "io.scalars", n * sizeof(fr_t), (void**)&d));
-    if (where == 0) {
-      BP_HIP(m, hipEventRecord(m->ev[4], m->stream));            // upload = ev[4] .. ev[0] (msm_launch records ev[0] first thing)
-      BP_HIP(m, hipMemcpyAsync(d, scalars, n * sizeof(fr_t), hipMemcpyHostToDevice, m->stream));
-    } else {
-      BP_HIP(m, hipStreamWaitEvent(m->stream, ready, 0));
-      if (!peer_path(m, src_device)) BP_HIP(m, hipMemcpyAsync(d, scalars, n * sizeof(fr_t), hipMemcpyDeviceToDevice, m->stream));
-      else BP_HIP(m, hipMemcpyPeerAsync(d, m->device, scalars, src_device, n * sizeof(fr_t), m->stream));
-    }
+    BP_HIP(m, hipEventRecord(m->ev[4], m->stream));            // upload = ev[4] .. ev[0] (msm_launch records ev[0] first thing)
+    BP_HIP(m, hipMemcpyAsync(d, scalars, n * sizeof(fr_t), hipMemcpyHostToDevice, m->stream));
     d_scalars = d;
+  } else if (where == 2 && n) {
+    BP_TRY(slices_from_leader(m, src_device, ready, 1, &src, &n, &d_scalars));
   }
   if (srs_tables_pay(*e, n)) return msm_launch(m, e->d_table + local_first, n, d_scalars, fmt, e->table_c, e->n, slot, d_blob, pend);
   return msm_launch(m, e->d_points28 + local_first, n, d_scalars, fmt, 0, 0, slot, d_blob, pend);
 }
 
-// sum_{i < n} s_i P_{first + i} over every shard of the SRS, in two steps so that several such sums can be in flight:
-// launch enqueues every shard's whole pipeline (result slot `slot` of each member), finish waits and adds the partial sums.
-struct ShardedPending {
-  std::vector<MsmPending> pend;
-  std::vector<bool> used;
-  bool host_scalars = false;
-};
-static int msm_all_shards_launch(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
-                                 int scalars_on_device, int slot, ShardedPending* sp) {
-  std::vector<SrsShard> sh;
-  BP_TRY(srs_shards(ctx, srs_handle, &sh, first, n_scalars));            // more scalars than points: cut to the SRS (zip() truncation, msm.rs:29)
-  if (first > sh[0].e->n_global) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds");
-  if (sh.size() > 1 && scalars_on_device) {            // the members' copies must see what the leader's stream has produced
+// sum_{i < n} s_i P_{first + i} over the shards sh of an SRS (srs_shards), in two steps so that several such sums can be in flight:
+// launch enqueues every shard's whole pipeline (result slot `slot` of each member; f[r] is member r's), finish waits and adds the
+// partial sums.  More scalars than points: cut to the SRS (shard_cut).
+static int msm_all_shards_launch(bp_ctx* ctx, const std::vector<SrsShard>& sh, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
+                                 int scalars_on_device, int slot, MsmFlight* f) {
+  const size_t R = sh.size();
+  for (size_t r = 0; r < R; r++) f[r].on = sh[r].m;
+  if (R > 1 && scalars_on_device) {            // the members' copies must see what the leader's stream has produced
     DeviceGuard guard(ctx->device);
     BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
   }
-  sp->pend.assign(sh.size(), MsmPending());
-  sp->used.assign(sh.size(), false);
-  sp->host_scalars = !scalars_on_device;
+  // a shard none of the range lies on is skipped -- except the only shard of a plain context: the empty MSM resets the stats and yields the identity
+  auto cut = [&](size_t r, size_t* lo, size_t* hi) {
+    shard_cut(first, n_scalars, sh[0].e->n_global, sh[r].e->first, sh[r].e->n, lo, hi);
+    return *lo < *hi || R == 1;
+  };
+  auto take = [&](size_t r) {
+    size_t lo, hi;
+    return cut(r, &lo, &hi);
+  };
+  auto launch_one = [&](size_t r) {
+    const SrsShard& s = sh[r];
+    size_t lo, hi;
+    cut(r, &lo, &hi);
+    const bool any = lo < hi;
+    const int where = !scalars_on_device ? 0 : (r == 0 ? 1 : 2);
+    msm_flight_launched(f[r], s.m, msm_shard_launch(s.m, s.e, any ? lo - s.e->first : 0, (const uint8_t*)scalars + (any ? (lo - first) * sizeof(fr_t) : 0),
+                                                    any ? hi - lo : 0, scalar_fmt, where, ctx->device, ctx->ev[4], slot, nullptr, &f[r].pend));
+  };
   // the launches: scalars already in HBM are enqueued by this thread (asynchronous copies and kernels);
   // host scalars go through the members' own threads, so that the uploads -- staged by the issuing thread when the memory is
   // pageable, as a Rust Vec<Scalar> is -- run on all PCIe links at once instead of one after another
-  std::vector<int> rcs(sh.size(), BP_OK);
-  std::vector<bool> take(sh.size(), false);
-  // a shard none of the range lies on is skipped -- except the only shard of a plain context: the empty MSM resets the stats and yields the identity
-  for (size_t r = 0; r < sh.size(); r++) take[r] = sh[r].lo < sh[r].hi || sh.size() == 1;
-  auto launch_one = [&](size_t r) {
-    const SrsShard& s = sh[r];
-    const bool any = s.lo < s.hi;
-    const int where = !scalars_on_device ? 0 : (r == 0 ? 1 : 2);
-    rcs[r] = msm_shard_launch(s.m, s.e, any ? s.lo - s.e->first : 0, (const uint8_t*)scalars + (any ? (s.lo - first) * sizeof(fr_t) : 0), any ? s.hi - s.lo : 0,
-                              scalar_fmt, where, ctx->device, ctx->ev[4], slot, nullptr, &sp->pend[r]);
-  };
-  if (!scalars_on_device && sh.size() > 1) {
-    over_members(ctx, sh.size(), [&](size_t r) { return (bool)take[r]; }, launch_one);
+  if (!scalars_on_device && R > 1) {
+    over_members(ctx, R, take, launch_one);
   } else {
-    for (size_t r = 0; r < sh.size(); r++)
-      if (take[r]) launch_one(r);
+    for (size_t r = 0; r < R; r++)
+      if (take(r)) launch_one(r);
   }
-  int rc = BP_OK;
-  for (size_t r = 0; r < sh.size(); r++) {
-    if (!take[r]) continue;
-    sp->used[r] = rcs[r] == BP_OK;             // a shard that failed to launch has nothing to wait for
-    const int rc1 = lift(ctx, sh[r].m, rcs[r]);
-    if (rc == BP_OK) rc = rc1;
-  }
-  return rc;               // the caller still finishes whatever was launched
+  for (size_t r = 0; r < R; r++)
+    if (f[r].rc != BP_OK) return lift(ctx, f[r].on, f[r].rc);
+  return BP_OK;               // either way the caller finishes whatever was launched
 }
-static int msm_all_shards_finish(bp_ctx* ctx, const ShardedPending& sp, int rc, g1_proj* out) {
-  const std::vector<bp_ctx*> sh = shards_of(ctx);
-  const std::vector<MsmPending>& pend = sp.pend;
-  const std::vector<bool>& used = sp.used;
-  if (pend.size() != sh.size()) return rc != BP_OK ? rc : BP_ERR_INVALID_ARG;      // nothing was launched (bad handle / offset)
-  // every launched shard is waited for, also after a failure elsewhere.  In a group the waits and the host epilogues (window
-  // sums -> Horner, ~0.1 ms each) run on the members' own threads: eight in sequence would cost more than the shards' GPU time
-  // of a 2^20-point MSM split eight ways.
-  std::vector<g1_proj> part(sh.size());
-  std::vector<int> rcs(sh.size(), BP_OK);
-  over_members(ctx, sh.size(), [&](size_t r) { return (bool)used[r]; }, [&](size_t r) {
-    DeviceGuard guard(sh[r]->device);
-    rcs[r] = msm_finish(sh[r], pend[r], &part[r]);
-    sh[r]->shard_accumulate_ms = sh[r]->msm_accumulate_ms;
-    sh[r]->shard_total_ms = sh[r]->msm_total_ms;
-    sh[r]->shard_adds = sh[r]->msm_adds;
-    sh[r]->msm_upload_ms = 0;
-    if (rcs[r] == BP_OK && sp.host_scalars && !pend[r].empty && hipEventElapsedTime(&sh[r]->msm_upload_ms, sh[r]->ev[4], sh[r]->ev[0]) != hipSuccess) {
-      (void)hipGetLastError();
-      sh[r]->msm_upload_ms = 0;
-    }
-  });
+static int msm_all_shards_finish(bp_ctx* ctx, MsmFlight* f, size_t R, bool host_scalars, int rc, g1_proj* out) {
+  rc = msm_finish_all(ctx, f, R, rc);
   g1_proj acc = g1_identity();
   float acc_ms = 0, dev_ms = 0;
   uint64_t adds = 0;
-  for (size_t r = 0; r < sh.size(); r++) {
-    if (!used[r]) continue;
-    const int rc1 = lift(ctx, sh[r], rcs[r]);
-    if (rc1 != BP_OK) {
-      if (rc == BP_OK) rc = rc1;
-      continue;
+  for (size_t r = 0; r < R; r++) {
+    if (!f[r].launched) continue;
+    bp_ctx* m = f[r].on;
+    m->shard_accumulate_ms = m->msm_accumulate_ms;
+    m->shard_total_ms = m->msm_total_ms;
+    m->shard_adds = m->msm_adds;
+    m->msm_upload_ms = 0;
+    if (f[r].rc != BP_OK) continue;
+    if (host_scalars && !f[r].pend.empty) {
+      DeviceGuard guard(m->device);
+      if (hipEventElapsedTime(&m->msm_upload_ms, m->ev[4], m->ev[0]) != hipSuccess) {
+        (void)hipGetLastError();
+        m->msm_upload_ms = 0;
+      }
     }
-    if (sh.size() == 1) acc = part[r]; else g1_add(acc, acc, part[r]);
-    acc_ms = std::max(acc_ms, sh[r]->msm_accumulate_ms);
-    dev_ms = std::max(dev_ms, sh[r]->msm_total_ms);
-    adds += sh[r]->msm_adds;
+    if (R == 1) acc = f[r].out[0]; else g1_add(acc, acc, f[r].out[0]);
+    acc_ms = std::max(acc_ms, m->msm_accumulate_ms);
+    dev_ms = std::max(dev_ms, m->msm_total_ms);
+    adds += m->msm_adds;
   }
   if (rc != BP_OK) return rc;
-  if (sh.size() > 1) {                                   // stats of a group: the slowest shard, all additions
+  if (R > 1) {                                   // stats of a group: the slowest shard, all additions
     ctx->msm_accumulate_ms = acc_ms;
     ctx->msm_total_ms = dev_ms;
     ctx->msm_adds = adds;
@@ -133,86 +156,47 @@ static int msm_all_shards_finish(bp_ctx* ctx, const ShardedPending& sp, int rc, 
 }
 static int msm_all_shards(bp_ctx* ctx, uint64_t srs_handle, size_t first, const void* scalars, size_t n_scalars, int scalar_fmt,
                           int scalars_on_device, g1_proj* out) {
-  ShardedPending sp;
-  const int rc = msm_all_shards_launch(ctx, srs_handle, first, scalars, n_scalars, scalar_fmt, scalars_on_device, 0, &sp);
-  return msm_all_shards_finish(ctx, sp, rc, out);
+  std::vector<SrsShard> sh;
+  BP_TRY(srs_shards(ctx, srs_handle, &sh));
+  if (first > sh[0].e->n_global) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "SRS offset out of bounds");
+  std::vector<MsmFlight> f(sh.size());
+  const int rc = msm_all_shards_launch(ctx, sh, first, scalars, n_scalars, scalar_fmt, scalars_on_device, 0, f.data());
+  return msm_all_shards_finish(ctx, f.data(), f.size(), !scalars_on_device, rc, out);
 }
 
 
 namespace bp {
-constexpr int MAX_LANES = 3;
-
-// k commitments of HBM-resident coefficient vectors (on the leader) over the members of a group: per batch of up to MSM_MAX_BATCH
-// vectors every member receives its slice of each (peer copies behind the leader's event), runs ONE pipeline over the slices'
-// bucket sets and delivers one partial sum per vector; the host adds the members' partial sums.  BP_ERR_TOO_LARGE before anything
-// was launched = a member's batch does not fit one pipeline.
-static int commit_many_group_batched(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out) {
-  std::vector<SrsShard> sh;
-  BP_TRY(srs_shards(ctx, srs_handle, &sh));
-  const size_t R = sh.size(), n_global = sh[0].e->n_global;
-  for (const SrsShard& s : sh)
-    if (!s.e->d_table) return BP_ERR_TOO_LARGE;
-  for (int base = 0; base < k; base += MSM_MAX_BATCH) {
-    const int cnt = std::min((int)MSM_MAX_BATCH, k - base);
-    {
-      DeviceGuard guard(ctx->device);
-      BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on the leader's stream
-    }
-    std::vector<MsmPending> pend(R);
-    std::vector<int> rcs(R, BP_OK);
-    std::vector<bool> used(R, false);
-    int rc = BP_OK;
-    for (size_t r = 0; r < R && rc == BP_OK; r++) {
-      bp_ctx* m = sh[r].m;
-      const SrsEntry* e = sh[r].e;
-      DeviceGuard guard(m->device);
-      const fr_t* ptrs[MSM_MAX_BATCH];
-      size_t lens[MSM_MAX_BATCH], total = 0;
-      for (int j = 0; j < cnt; j++) {
-        const size_t nj = std::min(n[base + j], n_global);              // zip() truncation, msm.rs:29
-        lens[j] = nj > e->first ? std::min(nj - e->first, e->n) : 0;
-        total += lens[j];
-      }
-      if (total == 0) continue;
-      if (r == 0) {
-        for (int j = 0; j < cnt; j++) ptrs[j] = d_coeffs[base + j] + e->first;
-      } else {
-        fr_t* d;
-        rc = lift(ctx, m, ws_get(m, "io.scalars", total * sizeof(fr_t), (void**)&d));
-        if (rc != BP_OK) break;
-        hipError_t he = hipStreamWaitEvent(m->stream, ctx->ev[4], 0);
-        size_t at = 0;
-        for (int j = 0; j < cnt && he == hipSuccess; j++) {
-          if (lens[j]) {
-            const fr_t* src = d_coeffs[base + j] + e->first;
-            if (!peer_path(m, ctx->device)) he = hipMemcpyAsync(d + at, src, lens[j] * sizeof(fr_t), hipMemcpyDeviceToDevice, m->stream);
-            else he = hipMemcpyPeerAsync(d + at, m->device, src, ctx->device, lens[j] * sizeof(fr_t), m->stream);
-          }
-          ptrs[j] = d + at;
-          at += lens[j];
-        }
-        if (he != hipSuccess) { rc = fail(ctx, BP_ERR_HIP, "commit batch: scalar slices", he, __FILE__, __LINE__); break; }
-      }
-      // (the tables are used whatever the slice lengths: skipping them for very short slices is a speed heuristic of the single path)
-      rcs[r] = msm_launch_many(m, e->d_table, (uint32_t)cnt, ptrs, lens, BP_FR_MONT, e->table_c, e->n, 0, nullptr, &pend[r]);
-      if (rcs[r] == BP_ERR_TOO_LARGE && r == 0 && base == 0) return BP_ERR_TOO_LARGE;
-      used[r] = rcs[r] == BP_OK;
-      rc = lift(ctx, m, rcs[r]);
-    }
-    std::vector<g1_proj> part(R * MSM_MAX_BATCH);
-    over_members(ctx, R, [&](size_t r) { return (bool)used[r]; }, [&](size_t r) {
-      DeviceGuard guard(sh[r].m->device);
-      rcs[r] = msm_finish(sh[r].m, pend[r], &part[r * MSM_MAX_BATCH]);
-    });
+// One round of COMMIT_GROUP_BATCH: cnt commitments of HBM-resident coefficient vectors (on the leader) over the members of a group.
+// Every member that holds a part of them receives its slice of each (slices_from_leader), runs ONE pipeline over the slices' bucket
+// sets and delivers one partial sum per vector; the host adds the members' partial sums.
+static int commit_group_batch_round(bp_ctx* ctx, const std::vector<SrsShard>& sh, const CommitShard* cs, const fr_t* const* d_coeffs, const size_t* n,
+                                    int cnt, g1_proj* out) {
+  const size_t R = sh.size();
+  {
+    DeviceGuard guard(ctx->device);
+    BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on the leader's stream
+  }
+  std::vector<MsmFlight> f(R);
+  for (size_t r = 0; r < R; r++) f[r].on = sh[r].m;
+  int rc = BP_OK;
+  for (size_t r = 0; r < R && rc == BP_OK; r++) {
+    bp_ctx* m = sh[r].m;
+    const SrsEntry* e = sh[r].e;
+    DeviceGuard guard(m->device);
+    const fr_t *src[MSM_MAX_BATCH], *ptrs[MSM_MAX_BATCH];
+    size_t lens[MSM_MAX_BATCH];
+    if (commit_slices(cs[r], sh[0].e->n_global, n, cnt, lens) == 0) continue;
+    for (int j = 0; j < cnt; j++) ptrs[j] = src[j] = d_coeffs[j] + (lens[j] ? e->first : 0);
+    int rc1 = r == 0 ? BP_OK : slices_from_leader(m, ctx->device, ctx->ev[4], cnt, src, lens, ptrs);
+    if (rc1 == BP_OK) rc1 = msm_launch_many(m, e->d_table, (uint32_t)cnt, ptrs, lens, BP_FR_MONT, e->table_c, e->n, 0, nullptr, &f[r].pend);
+    rc = lift(ctx, m, msm_flight_launched(f[r], m, rc1));
+  }
+  BP_TRY(msm_finish_all(ctx, f.data(), R, rc));
+  for (int j = 0; j < cnt; j++) {
+    g1_proj acc = g1_identity();
     for (size_t r = 0; r < R; r++)
-      if (used[r] && rc == BP_OK) rc = lift(ctx, sh[r].m, rcs[r]);
-    if (rc != BP_OK) return rc;
-    for (int j = 0; j < cnt; j++) {
-      g1_proj acc = g1_identity();
-      for (size_t r = 0; r < R; r++)
-        if (used[r]) g1_add(acc, acc, part[r * MSM_MAX_BATCH + j]);
-      out[base + j] = acc;
-    }
+      if (f[r].launched) g1_add(acc, acc, f[r].out[j]);
+    out[j] = acc;
   }
   return BP_OK;
 }
@@ -230,95 +214,79 @@ static int lane_get(bp_ctx* ctx, int j, bp_ctx** out) {
   *out = lane_of(ctx, j);
   return BP_OK;
 }
+// one commitment on a lane, behind `ready` (nullptr: the lane's own stream order is enough)
+static int lane_launch(bp_ctx* ctx, bp_ctx* lane, SrsEntry* e, const fr_t* d_coeffs, size_t n, hipEvent_t ready, MsmFlight* f) {
+  f->on = lane;
+  if (ready) BP_HIP(ctx, hipStreamWaitEvent(lane->stream, ready, 0));
+  const int rc = msm_shard_launch(lane, e, 0, d_coeffs, shard_slice(n, e->n_global, e->first, e->n), BP_FR_MONT, 1, ctx->device, nullptr, 0, nullptr, &f->pend);
+  return lift(ctx, lane, msm_flight_launched(*f, lane, rc));
+}
 
+static int commit_batch_knob() {
+  const char* v = knob("BP_COMMIT_BATCH");
+  return !v ? COMMIT_KNOB_UNSET : *v == '0' ? 0 : *v == '1' ? 1 : COMMIT_KNOB_UNSET;
+}
+
+// Setup::commit, k times: the route and its rounds are commit_plan's (commit_plan.hpp); each case below runs the rounds of one route.
 int commit_many(bp_ctx* ctx, uint64_t srs_handle, const fr_t* const* d_coeffs, const size_t* n, int k, g1_proj* out) {
   if (k <= 0) return BP_OK;
-  SrsEntry* e;
-  BP_TRY(srs_find(ctx, srs_handle, &e));
-  if (is_group(ctx) && k > 1 && e->d_table) {   // group: ONE pipeline per member over its slices of up to MSM_MAX_BATCH commitments
-    const char* v = knob("BP_COMMIT_BATCH");
-    if (!(v && *v == '0')) {
-      int rc = commit_many_group_batched(ctx, srs_handle, d_coeffs, n, k, out);
-      if (rc != BP_ERR_TOO_LARGE) return rc;       // too long for one pipeline somewhere: queue the commitments one by one below
-    }
-  }
-  if (is_group(ctx) || k == 1) {            // group: every member queues its shards of up to MSM_SLOTS commitments back to back
-    for (int base = 0; base < k; base += MSM_SLOTS) {
-      const int cnt = std::min((int)MSM_SLOTS, k - base);
-      ShardedPending sp[MSM_SLOTS];
-      int rcs[MSM_SLOTS], rc = BP_OK;
-      for (int j = 0; j < cnt; j++) rcs[j] = rc == BP_OK ? (rc = msm_all_shards_launch(ctx, srs_handle, 0, d_coeffs[base + j], n[base + j], BP_FR_MONT, 1, j, &sp[j])) : BP_OK;
-      for (int j = 0; j < cnt; j++) {
-        if (sp[j].pend.empty()) continue;
-        const int rc1 = msm_all_shards_finish(ctx, sp[j], rcs[j], &out[base + j]);
-        if (rc == BP_OK) rc = rc1;
+  std::vector<SrsShard> sh;
+  BP_TRY(srs_shards(ctx, srs_handle, &sh));
+  const size_t R = sh.size();
+  SrsEntry* e = sh[0].e;
+  std::vector<CommitShard> cs(R);
+  for (size_t r = 0; r < R; r++) cs[r] = {sh[r].e->first, sh[r].e->n, sh[r].e->d_table ? sh[r].e->table_c : 0u};
+  const CommitPlan plan = commit_plan(cs.data(), R, e->n_global, k, n, is_group(ctx), commit_batch_knob(), msm_knobs());
+  switch (plan.route) {
+    case COMMIT_GROUP_BATCH:
+      for (const CommitRound& rd : plan.rounds) BP_TRY(commit_group_batch_round(ctx, sh, cs.data(), d_coeffs + rd.base, n + rd.base, rd.cnt, out + rd.base));
+      return BP_OK;
+    case COMMIT_SHARDED:
+      for (const CommitRound& rd : plan.rounds) {            // every member queues its shards of the round's commitments back to back
+        std::vector<MsmFlight> f(R * rd.cnt);
+        int rcs[MSM_SLOTS], tried = 0, rc = BP_OK;
+        for (; tried < rd.cnt && rc == BP_OK; tried++)
+          rcs[tried] = rc = msm_all_shards_launch(ctx, sh, 0, d_coeffs[rd.base + tried], n[rd.base + tried], BP_FR_MONT, 1, tried, &f[R * tried]);
+        for (int j = 0; j < tried; j++) {
+          const int rc1 = msm_all_shards_finish(ctx, &f[R * j], R, false, rcs[j], &out[rd.base + j]);
+          if (rc == BP_OK) rc = rc1;
+        }
+        BP_TRY(rc);
       }
-      if (rc != BP_OK) return rc;
-    }
-    return BP_OK;
-  }
-  DeviceGuard guard(ctx->device);
-  // One pipeline over the bucket sets of up to MSM_MAX_BATCH commitments (msm_launch_many): one sort keyed (polynomial, bucket),
-  // one accumulation, one fix-up, one tree over J x 2^(c-1) buckets -- the latency-bound tail is paid once per round instead of
-  // once per commitment.  Needs the SRS's fixed-base tables and a batch short enough for the partition sort.  On ONE device the
-  // concurrent lanes below already hide the tails of two commitments under the accumulation of the third, and the batch's
-  // three-fold sort is exposed: measured 35.6 ms per 2^20-gate proof against 34.4-35.4 with lanes (profiles/r03_commit_batch_ab.txt),
-  // so the batch runs only on request there (BP_COMMIT_BATCH=1).  The members of a group context, whose shards are short and whose
-  // pipelines share one stream each, use it by default (above).
-  {
-    const char* v = knob("BP_COMMIT_BATCH");
-    size_t n_max = 0;
-    for (int j = 0; j < k; j++) n_max = std::max(n_max, std::min(n[j], e->n));
-    if (srs_tables_pay(*e, n_max) && v && *v == '1') {
-      bool ok = true;
-      for (int base = 0; base < k && ok; base += (int)MSM_MAX_BATCH) {
-        const int cnt = std::min((int)MSM_MAX_BATCH, k - base);
-        const fr_t* ptrs[MSM_MAX_BATCH];
+      return BP_OK;
+    case COMMIT_DEVICE_BATCH: {
+      DeviceGuard guard(ctx->device);
+      for (const CommitRound& rd : plan.rounds) {
         size_t lens[MSM_MAX_BATCH];
-        for (int j = 0; j < cnt; j++) {
-          ptrs[j] = d_coeffs[base + j];
-          lens[j] = std::min(n[base + j], e->n);                        // zip() truncation, msm.rs:29
-        }
+        commit_slices(cs[0], e->n_global, n + rd.base, rd.cnt, lens);
         MsmPending pend;
-        int rc = msm_launch_many(ctx, e->d_table, (uint32_t)cnt, ptrs, lens, BP_FR_MONT, e->table_c, e->n, 0, nullptr, &pend);
-        if (rc == BP_ERR_TOO_LARGE && base == 0) {                      // too long for one pipeline: the lanes below
-          ok = false;
-          break;
+        BP_TRY(msm_launch_many(ctx, e->d_table, (uint32_t)rd.cnt, d_coeffs + rd.base, lens, BP_FR_MONT, e->table_c, e->n, 0, nullptr, &pend));
+        BP_TRY(msm_finish(ctx, pend, &out[rd.base]));
+      }
+      return BP_OK;
+    }
+    case COMMIT_LANES: {
+      DeviceGuard guard(ctx->device);
+      bp_ctx* last;
+      BP_TRY(lane_get(ctx, plan.width < k ? plan.width - 1 : k - 1, &last));      // every lane the rounds below use exists before the first launch
+      for (const CommitRound& rd : plan.rounds) {
+        BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on ctx->stream
+        MsmFlight f[MAX_LANES];
+        int rc = BP_OK;
+        for (int j = 0; j < rd.cnt && rc == BP_OK; j++)
+          rc = lane_launch(ctx, lane_of(ctx, j), e, d_coeffs[rd.base + j], n[rd.base + j], j ? ctx->ev[4] : nullptr, &f[j]);
+        rc = msm_finish_all(ctx, f, rd.cnt, rc);
+        for (int j = 0; j < rd.cnt; j++) {
+          if (!f[j].launched || f[j].rc != BP_OK) continue;
+          out[rd.base + j] = f[j].out[0];
+          if (f[j].on->msm_accumulate_ms > ctx->msm_accumulate_ms) ctx->msm_accumulate_ms = f[j].on->msm_accumulate_ms;
         }
-        if (rc != BP_OK) return rc;
-        BP_TRY(msm_finish(ctx, pend, &out[base]));
+        BP_TRY(rc);
       }
-      if (ok) return BP_OK;
+      return BP_OK;
     }
   }
-  bp_ctx* last;
-  BP_TRY(lane_get(ctx, std::min(MAX_LANES, k) - 1, &last));          // every lane the rounds below use exists before the first launch
-  for (int base = 0; base < k; base += MAX_LANES) {
-    const int cnt = std::min(MAX_LANES, k - base);
-    BP_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));          // the coefficient vectors were produced on ctx->stream
-    MsmPending pend[MAX_LANES];
-    bool used[MAX_LANES] = {false, false, false};
-    int rc = BP_OK;
-    for (int j = 0; j < cnt && rc == BP_OK; j++) {
-      bp_ctx* lane = lane_of(ctx, j);
-      if (lane != ctx) {
-        hipError_t he = hipStreamWaitEvent(lane->stream, ctx->ev[4], 0);
-        if (he != hipSuccess) { rc = fail(ctx, BP_ERR_HIP, "commit lane wait", he, __FILE__, __LINE__); break; }
-      }
-      const size_t cnt_j = std::min(n[base + j], e->n);              // zip() truncation, msm.rs:29
-      rc = lift(ctx, lane, msm_shard_launch(lane, e, 0, d_coeffs[base + j], cnt_j, BP_FR_MONT, 1, ctx->device, nullptr, 0, nullptr, &pend[j]));
-      used[j] = rc == BP_OK;
-    }
-    for (int j = 0; j < cnt; j++) {                                 // every launched lane is waited for, also after a failure elsewhere
-      if (!used[j]) continue;
-      bp_ctx* lane = lane_of(ctx, j);
-      const int rc1 = lift(ctx, lane, msm_finish(lane, pend[j], &out[base + j]));
-      if (rc == BP_OK) rc = rc1;
-      if (lane != ctx && rc1 == BP_OK && lane->msm_accumulate_ms > ctx->msm_accumulate_ms) ctx->msm_accumulate_ms = lane->msm_accumulate_ms;
-    }
-    if (rc != BP_OK) return rc;
-  }
-  return BP_OK;
+  return BP_ERR_INVALID_ARG;
 }
 
 int commit_lane_launch(bp_ctx* ctx, int j, uint64_t srs_handle, const fr_t* d_coeffs, size_t n, hipEvent_t ready, MsmPending* pend) {
@@ -329,8 +297,10 @@ int commit_lane_launch(bp_ctx* ctx, int j, uint64_t srs_handle, const fr_t* d_co
   DeviceGuard guard(ctx->device);
   bp_ctx* lane;
   BP_TRY(lane_get(ctx, j, &lane));
-  BP_HIP(ctx, hipStreamWaitEvent(lane->stream, ready, 0));
-  return lift(ctx, lane, msm_shard_launch(lane, e, 0, d_coeffs, std::min(n, e->n), BP_FR_MONT, 1, ctx->device, nullptr, 0, nullptr, pend));     // zip() truncation, msm.rs:29
+  MsmFlight f;
+  const int rc = lane_launch(ctx, lane, e, d_coeffs, n, ready, &f);
+  *pend = f.pend;
+  return rc;
 }
 int commit_lane_finish(bp_ctx* ctx, int j, const MsmPending& pend, g1_proj* out) {
   bp_ctx* lane = lane_of(ctx, j);
@@ -399,8 +369,8 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
   BP_TRY(ws_get(ctx, "seam.p28", n * sizeof(g1_affine28), (void**)&d_p28));
   BP_TRY(ws_get(ctx, "seam.scalars", n * sizeof(fr_t), (void**)&d_scal));
   BP_HIP(ctx, stream_wait(ctx->stream));                 // the workspaces may still be read by work the caller enqueued before
-  MsmPending pend[SEAM_PIECES];
-  int launched = 0, rc = BP_OK;
+  MsmFlight f[SEAM_PIECES];
+  int rc = BP_OK;
   for (int k = 0; k < pieces && rc == BP_OK; k++) {
     const size_t lo = (size_t)k * piece, cnt = lo < n ? std::min(piece, n - lo) : 0;
     if (!cnt) break;
@@ -422,24 +392,19 @@ int bp_msm_g1_projective144(bp_ctx* ctx, const uint8_t* points144, size_t n_poin
       rc = fail(ctx, BP_ERR_HIP, "bucket_msm piece order", he, __FILE__, __LINE__);
       break;
     }
-    rc = msm_launch(ctx, d_p28 + lo, cnt, d_scal + lo, scalar_fmt, 0, 0, k, nullptr, &pend[k]);
-    if (rc == BP_OK) launched = k + 1;
+    rc = msm_flight_launched(f[k], ctx, msm_launch(ctx, d_p28 + lo, cnt, d_scal + lo, scalar_fmt, 0, 0, k, nullptr, &f[k].pend));
   }
-  // every launched piece is finished (waited for) even after an error: the pinned slots and workspaces must be quiet on return
-  g1_proj acc = g1_identity();
-  uint64_t adds = 0;
-  for (int k = 0; k < launched; k++) {
-    g1_proj part;
-    const int r2 = msm_finish(ctx, pend[k], &part);
-    if (r2 != BP_OK && rc == BP_OK) rc = r2;
-    if (r2 == BP_OK) {
-      g1_add(acc, acc, part);
-      adds += pend[k].adds;
-    }
-  }
+  rc = msm_finish_all(ctx, f, pieces, rc);
   if (rc != BP_OK) {
     (void)stream_wait(side->stream);
     return rc;
+  }
+  g1_proj acc = g1_identity();
+  uint64_t adds = 0;
+  for (int k = 0; k < pieces; k++) {
+    if (!f[k].launched) continue;
+    g1_add(acc, acc, f[k].out[0]);
+    adds += f[k].pend.adds;
   }
   ctx->msm_adds = adds;
   host_encode96(out96, acc);

@@ -41,11 +41,10 @@ int srs_find(bp_ctx* ctx, uint64_t handle, SrsEntry** out) {
   return BP_OK;
 }
 // The one walk from a handle to its shards (capi_common.hpp): member r's entry under the handle the leader's entry lists for it
-// (a plain context has only its own), and the part of [first, first + n) on it -- n cut to the SRS's length first (zip(), msm.rs:29).
+// (a plain context has only its own), and the part of [first, first + n) on it (shard_cut, commit_plan.hpp).
 int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, size_t first, size_t n) {
   SrsEntry* lead;
   BP_TRY(srs_find(ctx, srs_handle, &lead));
-  const size_t end = first > lead->n_global ? first : first + std::min(n, lead->n_global - first);
   const std::vector<bp_ctx*> sh = shards_of(ctx);
   out->resize(sh.size());
   for (size_t r = 0; r < sh.size(); r++) {
@@ -53,8 +52,7 @@ int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, siz
     s.m = sh[r];
     s.handle = lead->member_handle.empty() ? srs_handle : lead->member_handle[r];
     BP_TRY(lift(ctx, s.m, srs_find(s.m, s.handle, &s.e)));
-    s.lo = std::max(first, s.e->first);
-    s.hi = std::min(end, s.e->first + s.e->n);
+    shard_cut(first, n, lead->n_global, s.e->first, s.e->n, &s.lo, &s.hi);
   }
   return BP_OK;
 }

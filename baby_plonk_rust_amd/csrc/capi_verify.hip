@@ -177,25 +177,17 @@ static int verify_reduce_run(bp_ctx* ctx, uint32_t log_n, const uint8_t vk768[76
 
   // stage 4: B over all 9 m + 9 points, A over the slice [7 m, 9 m) of the same array
   BP_TRY(srs_to28_into(ctx, d_pts, n_all, d_p28));
-  MsmPending pend_b, pend_a;
-  BP_TRY(msm_launch(ctx, d_p28, n_all, d_b, BP_FR_MONT, 0, 0, 0, nullptr, &pend_b));
-  int rc = msm_launch(ctx, d_p28 + 7 * m, 2 * m, d_a, BP_FR_MONT, 0, 0, 1, nullptr, &pend_a);
-  const bool a_launched = rc == BP_OK;
-  if (a_launched) {
+  MsmFlight f[2];                                                  // [0] B, [1] A
+  int rc = msm_flight_launched(f[0], ctx, msm_launch(ctx, d_p28, n_all, d_b, BP_FR_MONT, 0, 0, 0, nullptr, &f[0].pend));
+  if (rc == BP_OK) rc = msm_flight_launched(f[1], ctx, msm_launch(ctx, d_p28 + 7 * m, 2 * m, d_a, BP_FR_MONT, 0, 0, 1, nullptr, &f[1].pend));
+  if (rc == BP_OK) {
     hipError_t he = hipEventRecord(ev[5], st);
     if (he != hipSuccess) rc = fail(ctx, BP_ERR_HIP, "hipEventRecord", he, __FILE__, __LINE__);
   }
-  g1_proj A = g1_identity(), B = g1_identity();
-  const int rb = msm_finish(ctx, pend_b, &B);                      // every launched MSM is waited for, also after an error
-  if (rc == BP_OK) rc = rb;
-  if (a_launched) {
-    const int ra = msm_finish(ctx, pend_a, &A);
-    if (rc == BP_OK) rc = ra;
-  }
-  BP_TRY(rc);
+  BP_TRY(msm_finish_all(ctx, f, 2, rc));
   for (int k = 0; k < 5; k++) BP_HIP(ctx, hipEventElapsedTime(&ctx->verify_ms[k], ev[k], ev[k + 1]));
-  host_encode96(out192, A);
-  host_encode96(out192 + 96, B);
+  host_encode96(out192, f[1].out[0]);
+  host_encode96(out192 + 96, f[0].out[0]);
   return BP_OK;
 }
 

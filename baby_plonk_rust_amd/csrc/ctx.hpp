@@ -299,8 +299,7 @@ int pinned_get(bp_ctx* ctx, size_t bytes, void** out);
 // ---- launchers implemented in msm.hip / ntt.hip / poly.hip / srs.hip --------------------------------
 // One MSM = msm_launch (everything enqueued on ctx->stream, nothing waited for) + msm_finish (wait, status, host epilogue).
 // The split lets one host thread keep several devices (or several MSMs of one stream) in flight.  `slot` selects one of
-// MSM_SLOTS result areas in the pinned staging buffer; launches on one stream reuse the device workspaces in stream order.
-constexpr int MSM_SLOTS = 4;
+// MSM_SLOTS (msm_plan.hpp) result areas in the pinned staging buffer; launches on one stream reuse the device workspaces in stream order.
 struct MsmPending {
   bool empty = true, blob = false;
   bool tables = false;                  // fixed-base window tables (false: per-window buckets)
@@ -320,6 +319,27 @@ int msm_blobs_sum_device_run(bp_ctx* ctx, const void* d_blobs, size_t n_blobs, v
 int msm_blob_poisoned(const uint8_t* blobs, size_t n_blobs, uint32_t* rank);
 int msm_blob_poison_run(bp_ctx* ctx, void* d_blob, int err, uint32_t rank);
 int msm_finish(bp_ctx* ctx, const MsmPending& pend, g1_proj* host_out);
+// One MSM in flight beside others: the context it runs on (the caller's, a member, a lane), what its launch returned, its results.
+struct MsmFlight {
+  bp_ctx* on = nullptr;
+  MsmPending pend;
+  bool launched = false;                // false: nothing to wait for (not reached, or the launch failed: rc says which)
+  int rc = BP_OK;                       // of the launch; of msm_finish once msm_finish_all has run
+  g1_proj out[MSM_MAX_BATCH];           // pend.J results (msm_finish_all)
+};
+inline int msm_flight_launched(MsmFlight& f, bp_ctx* on, int launch_rc) {
+  f.on = on;
+  f.rc = launch_rc;
+  f.launched = launch_rc == BP_OK;
+  return launch_rc;
+}
+// THE rule of every caller that has several MSMs in flight (capi_msm.hip): every launched one is finished -- waited for -- also after
+// a failure elsewhere, because the pinned result slots and the grow-only workspaces of its context must be quiet before the call
+// returns (the next call reuses the slots, and ws_get frees a workspace it has to grow).  The first error is reported on ctx, the
+// context the caller holds: `rc`, what the launches returned (its text is on ctx already), else the first failing flight's in
+// array order.  Flights f[r] on the members r of a group are finished on the members' own threads (over_members); any other set
+// in order on the calling thread.  Adds no points and touches no stats: each caller does that with f[i].out and f[i].on.
+int msm_finish_all(bp_ctx* ctx, MsmFlight* f, size_t count, int rc);
 int msm_run(bp_ctx* ctx, const g1_affine28* d_points28, size_t n, const fr_t* d_scalars, int fmt, uint32_t table_c, size_t table_stride,
             g1_proj* host_out);
 int msm_init_device(bp_ctx* ctx);

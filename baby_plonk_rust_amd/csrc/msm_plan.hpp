@@ -18,6 +18,7 @@ constexpr int MSM_MAX_TABLE_C = 24;      // fixed-base tables: partitioned count
 constexpr uint32_t MSM_HIST_LOG = 15;    // buckets per LDS histogram (128 KiB of the 160)
 constexpr int MSM_MAX_WINDOWS = 128;
 constexpr uint32_t MSM_MAX_BATCH = 4;    // scalar vectors in one pipeline (MsmScalars)
+constexpr int MSM_SLOTS = 4;             // result areas of a context's pinned staging buffer: its MSMs in flight together
 constexpr uint32_t SCAN_TILE = 4096;     // counts per workgroup of the scan_* kernels
 constexpr uint32_t RADIX_SLICE = 8192;   // records per workgroup pass of msm_radix_count / _scatter
 constexpr uint32_t PART_MAX_BITS = 12, PART_MAX = 1u << PART_MAX_BITS;      // partitions of msm_part_count / _scatter

@@ -1,6 +1,6 @@
 """-m gpu: the J-vector MSM pipeline (msm_launch_many with J > 1: one sort keyed (vector, bucket), one accumulation, one fix-up, one tree over
 J * 2^(c-1) buckets, J Horner passes) at every edge it has of its own.  The vehicle is what ships: bp_commit_many_device on a group context
-(commit_many_group_batched), here a rehearsal group of two members on device 0 with m points each, over an SRS of 2 m points
+(the COMMIT_GROUP_BATCH route of commit_many), here a rehearsal group of two members on device 0 with m points each, over an SRS of 2 m points
 P_i = (a + i d) G with fixed-base tables of a chosen width.  Every commitment is held by itself against the closed form
 (sum_i s_i (a + i d)) G in Python integers -- never against the library -- and against bp_commit_device of the same polynomial, bytes for
 bytes; every shape asserts the path the library reports for it (Context.msm_path), so a retune that moves a shape off the branch it was
@@ -186,11 +186,12 @@ def test_three_members_and_their_seams():
 
 
 def test_the_retreat_to_one_by_one():
-    """A batch too long for the partition sort is refused (BP_ERR_TOO_LARGE inside the library) and the call redone one commitment at a time.
+    """A batch too long for the partition sort would be refused (BP_ERR_TOO_LARGE inside the library): commit_many asks the plan of every round
+    before it launches anything (csrc/commit_plan.hpp; the same edge without a GPU: tests/test_commit_plan.py) and goes one commitment at a time.
     c = 16, W = 16, J = 4: kb = 17; pb reaches 13 from 12 288 * 2^13 entries on, and the rule that keeps pb at PART_MAX_BITS = 12 holds
     while entries >> 12 <= 32 768, i.e. below 32 769 * 4 096 = 2^27 + 4 096 = 134 221 824 entries = W * n * J = 64 n: refused from
     n = 2 097 216 points per member (the packed rule does not apply: kb + vb = 17 + 27 = 44 <= 32 + 13).  Refused at the first batch, and at
-    a later batch after the first one ran; the context works for a small batch afterwards."""
+    a later batch while the first one fits; the context works for a small batch afterwards."""
     import torch
     m, c = 2097216, 16
     ctx = bp.Context([0, 0])
@@ -218,7 +219,7 @@ def test_the_retreat_to_one_by_one():
     assert ctx.msm_path(0)["J"] == 1 and ctx.msm_path(0)["c"] == 16
     # a small batch in between: the next call starts from a context that last ran J = 4
     assert bp.commit_many_device(setup, short) == want_short and ctx.msm_path(0)["J"] == 4
-    # 2. the first batch runs, the second is refused: everything is redone one by one
+    # 2. the first batch fits, the second would be refused: everything goes one by one
     assert bp.commit_many_device(setup, short + full) == want_short + want
     assert ctx.msm_path(0)["J"] == 1
     # the context is usable for a batch afterwards

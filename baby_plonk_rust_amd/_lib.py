@@ -120,6 +120,10 @@ SIGNATURES = {
     "bp_kzg_open_all": (_int, [_vp, _u64, _vp, _sz, _int, _int, _u32, _vp, _vp]),
     "bp_kzg_open_all_device": (_int, [_vp, _u64, _vp, _sz, _int, _u32, _vp, _vp]),
     "bp_kzg_open_all_last_stats": (_int, [_vp, _vp]),
+    "bp_srs_open_cosets_prepare": (_int, [_vp, _u64, _u32, _u32]),
+    "bp_kzg_open_cosets": (_int, [_vp, _u64, _vp, _sz, _int, _int, _u32, _u32, _vp, _vp]),
+    "bp_kzg_open_cosets_device": (_int, [_vp, _u64, _vp, _sz, _int, _u32, _u32, _vp, _vp]),
+    "bp_kzg_verify_cells_reduce": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _int, _u32, _vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

@@ -1181,6 +1181,89 @@ class Setup:
         return pairing_check([pair], self.x_2, ctx=self.ctx, host=host)[0]
 
 
+    # ---- cell proofs: one proof per coset of cell_size points (bp_kzg_open_cosets, bp_kzg_verify_cells_reduce) ----
+    @staticmethod
+    def _cell_logs(name, group_order, cell_size):
+        for what, v in (("group_order", group_order), ("cell_size", cell_size)):
+            if v < 1 or v & (v - 1):
+                raise BpError(-2, name, "%s %d is not a power of two" % (what, v))
+        return group_order.bit_length() - 1, cell_size.bit_length() - 1
+
+    def prepare_open_cosets(self, group_order, cell_size):
+        """build and keep the table open_cosets needs for (group_order, cell_size) (bp_srs_open_cosets_prepare: 2 * group_order
+        points of HBM in the ONE table slot of this SRS, which prepare_open_all / open_all use with cell_size 1: another key
+        replaces the table).  Optional: open_cosets builds it on first use."""
+        log_n, log_l = self._cell_logs("Setup.prepare_open_cosets", group_order, cell_size)
+        c = self.ctx
+        c.check(c._lib.bp_srs_open_cosets_prepare(c._h, self.handle, log_n, log_l), "Setup.prepare_open_cosets")
+
+    def open_cosets(self, poly, cell_size, group_order=None):
+        """the group_order / cell_size CELL proofs of one Polynomial or DevicePolynomial in one call (bp_kzg_open_cosets /
+        bp_kzg_open_cosets_device): returns (cells [r, l, 4] uint64, proofs [r, 96] uint8), r = n / l.  Cell k is the coset
+        {w^(k + r j) : j < l} of the domain, cells[k, j] = f(w^(k + r j)), and proofs[k] = [q_k(tau)] G with
+        q_k = f div (x^l - w^(k l)) is its ONE proof.  Polynomial and Setup as for open_all (the first n - l points are used).
+        Claim k is then CellOpening(commitment, k, cells[k], bytes(proofs[k])).  cell_size == 1 is open_all."""
+        c = self.ctx
+        n = group_order
+        if n is None:
+            n = len(poly) if poly.basis == BASIS_LAGRANGE else max(1, 1 << max(len(poly) - 1, 0).bit_length())
+            n = max(n, cell_size)
+        log_n, log_l = self._cell_logs("Setup.open_cosets", n, cell_size)
+        r = max(n // cell_size, 1)
+        cells, proofs = np.zeros((r, cell_size, 4), dtype=np.uint64), np.zeros((r, 96), dtype=np.uint8)
+        head = (c._h, self.handle, poly._ptr() if len(poly) else None, len(poly), poly.basis)
+        fn = getattr(c._lib, "bp_kzg_open_cosets" + poly._SUFFIX)
+        c.check(fn(*head, *poly._FMT, log_n, log_l, cells.ctypes.data, proofs.ctypes.data), "Setup.open_cosets")
+        return cells, proofs
+
+    def cell_pairing_inputs(self, claims, group_order, weights=None, checks=0):
+        """the claims of a list of CellOpening records (one cell size for all) reduced to (A96, B96): they hold iff
+        pairing(A, [tau^cell_size]_2) == pairing(B, G2 generator) (bp_kzg_verify_cells_reduce).  weights: one scalar per claim,
+        drawn after the claims were received, >= 128 bits of entropy each (None: a single claim).  checks=1 adds the subgroup
+        test of every commitment and proof.  A rejected claim raises BpError with the lowest failing claim in `index`."""
+        claims = [claims] if isinstance(claims, CellOpening) else list(claims)
+        m = len(claims)
+        vals = [np.ascontiguousarray(o.values, dtype=np.uint64).reshape(-1, 4) for o in claims]
+        if len(set(len(v) for v in vals)) > 1:
+            raise BpError(-6, "Setup.cell_pairing_inputs", "every claim must have the same number of values")
+        l = len(vals[0]) if m else 1
+        log_n, log_l = self._cell_logs("Setup.cell_pairing_inputs", group_order, l)
+        com = np.frombuffer(b"".join(bytes(o.commitment) for o in claims), dtype=np.uint8).copy()
+        rec = np.frombuffer(b"".join(bytes(o.proof) for o in claims), dtype=np.uint8).copy()
+        if len(com) != 96 * m or len(rec) != 96 * m:
+            raise BpError(-6, "Setup.cell_pairing_inputs", "points: 96-byte records expected")
+        idx = np.array([o.index for o in claims], dtype=np.uint32)
+        v = np.ascontiguousarray(np.stack(vals)) if m else np.zeros((0, 4), np.uint64)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        if w is not None and w.size != 4 * m:
+            raise BpError(-6, "Setup.cell_pairing_inputs", "weights: %d scalars expected" % m)
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        c, out, bad = self.ctx, np.zeros(192, dtype=np.uint8), C.c_size_t(-1)
+        rc = c._lib.bp_kzg_verify_cells_reduce(c._h, self.handle, log_n, log_l, ptr(com), ptr(idx), ptr(v), ptr(rec), m, ptr(w), FR_MONT, checks,
+                                               out.ctypes.data, C.byref(bad))
+        try:
+            c.check(rc, "bp_kzg_verify_cells_reduce")
+        except BpError as e:
+            e.index = bad.value if rc in (-1, -3, -4) and bad.value != C.c_size_t(-1).value else None
+            raise
+        return out[:96].tobytes(), out[96:].tobytes()
+
+    def verify_cells(self, claims, group_order, tau_l_g2, weights=None, host=True):
+        """do the cell claims hold?  cell_pairing_inputs, then one pairing check against tau_l_g2 = [tau^cell_size]_2 (192 bytes,
+        the CALLER'S: a ceremony ships the G2 powers), on the host or on the GPU.  weights=None with several claims draws
+        128-bit weights here (the claims are in hand by then)."""
+        claims = [claims] if isinstance(claims, CellOpening) else list(claims)
+        if weights is None and len(claims) > 1:
+            import secrets
+            weights = scalars_from_ints([secrets.randbits(128) | 1 << 127 for _ in claims])
+        pair = self.cell_pairing_inputs(claims, group_order, weights)
+        return pairing_check([pair], tau_l_g2, ctx=self.ctx, host=host)[0]
+
+
+CellOpening = collections.namedtuple("CellOpening", "commitment index values proof")
+CellOpening.__doc__ = """one KZG cell claim: `commitment` (96 bytes) takes the values `values` ([l, 4], cell order) on cell `index` of its
+domain, with the proof `proof` (96 bytes) -- what Setup.commit and Setup.open_cosets return, put together"""
+
 Opening = collections.namedtuple("Opening", "commitments z ys nu proof")
 Opening.__doc__ = """one KZG claim: `commitments` (96 bytes, or a list of them) open at `z` to the values `ys` ([count, 4]), combined by
 `nu` (None for one polynomial), with the proof `proof` (96 bytes) -- what Setup.commit and Setup.open return, put together"""

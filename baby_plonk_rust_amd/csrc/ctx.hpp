@@ -60,6 +60,9 @@ struct SrsEntry {
   // the context's own device (a group: held by the leader's entry only); nullptr until the first call, replaced by another log_n
   g1_affine* d_open_all = nullptr;
   uint32_t open_all_log_n = 0;
+  // the cell size the table was built for (kzg_open_cosets.hpp: l = 2^open_all_log_l transforms of 2n / l points side by side); 0: open_all's.
+  // The slot's key is (open_all_log_n, open_all_log_l): a call with another key replaces the table.
+  uint32_t open_all_log_l = 0;
 };
 
 // preprocessed circuit of the native prover (prover.hip): CommonPreprocessedInput (program.rs:34-50) resident in HBM,
@@ -398,6 +401,14 @@ int open_all_table_run(bp_ctx* ctx, const g1_affine* d_srs, uint32_t log_n, g1_a
 int open_all_proofs_run(bp_ctx* ctx, const g1_affine* d_table, const fr_t* d_sc, uint32_t log_n, g1_affine* d_out, hipEvent_t mid);
 int open_all_twiddles_run(bp_ctx* ctx, uint32_t log_n);      // the buffers and twiddle tables of this log_n, made unless they are there (enqueued)
 int open_all_chat_run(bp_ctx* ctx, uint32_t log_n, const fr_t* d_f, size_t n_values, const fr_t& scale, fr_t* d_out);      // d_out[t] = scale c^_t, t < 2n
+// the n / l cell proofs (kzg_open_cosets.hpp), log_l < log_n < G1_NTT_MAX_LOG; log_l = 0 forwards to the open_all drivers above.  table:
+// d_table[j R + i] = DFT_R(S^(j))_i (2n points, R = 2n / l) of d_srs[0 .. n - l).  proofs: d_out[0 .. n / l) from the table and
+// d_sc[j R + i] = R^-1 DFT_R(c^(j))_i; `mid` is recorded in front of the final transform.  Both wait for the stream and append their pass times.
+int open_cosets_table_run(bp_ctx* ctx, const g1_affine* d_srs, uint32_t log_n, uint32_t log_l, g1_affine* d_table);
+int open_cosets_proofs_run(bp_ctx* ctx, const g1_affine* d_table, const fr_t* d_sc, uint32_t log_n, uint32_t log_l, g1_affine* d_out, hipEvent_t mid);
+int open_cosets_twiddles_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l);
+int open_cosets_chat_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const fr_t* d_f, size_t n_values, const fr_t& scale, fr_t* d_out);
+int open_cosets_cell_order_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const fr_t* d_in, fr_t* d_out);      // d_out[k l + j] = d_in[k + r j]
 // kzg.hip: the values y_j = f_j(z) (host_y, count of them) and the quotient (sum_j nu^j f_j - sum_j nu^j y_j) / (x - z) of count
 // <= 16 HBM-resident Montgomery polynomials, in the form they are held in; *d_q is a workspace of the context, *nq its length.
 // nu_pows: nu^0 .. nu^(count-1).  Lagrange: every column has 2^log_n values, the quotient too.  Monomial: nq = max_j n_j - 1 (0: no quotient).
@@ -405,6 +416,8 @@ int kzg_open_lagrange_run(bp_ctx* ctx, const fr_t* const* d_polys, size_t count,
                           fr_t* host_y, fr_t** d_q);
 int kzg_open_monomial_run(bp_ctx* ctx, const fr_t* const* d_polys, const size_t* n, size_t count, const fr_t& z, const fr_t* nu_pows,
                           fr_t* host_y, fr_t** d_q, size_t* nq);
+// cell claims: d_out[t] = - sum_{i<m} d_rho[i] d_w[i]^t d_c[i l + t], t < l = 2^log_l (Montgomery; enqueued on ctx->stream)
+int kzg_cells_combine_run(bp_ctx* ctx, const fr_t* d_c, const fr_t* d_w, const fr_t* d_rho, size_t m, uint32_t log_l, fr_t* d_out);
 
 void comm_release(bp_ctx* ctx);                 // capi_comm.hip: destroys the context's communicator, if any
 int side_ctx_get(bp_ctx* ctx, bp_ctx** out);       // creates ctx->side on first use (capi_ctx.hip)

@@ -117,4 +117,12 @@ int kzg_open_monomial_run(bp_ctx* ctx, const fr_t* const* d_polys, const size_t*
   return BP_OK;
 }
 
+// d_out[t] = - sum_i d_rho[i] d_w[i]^t d_c[i l + t], t < l (kzg_kernels.hpp: kzg_cells_combine); enqueued, not waited for
+int kzg_cells_combine_run(bp_ctx* ctx, const fr_t* d_c, const fr_t* d_w, const fr_t* d_rho, size_t m, uint32_t log_l, fr_t* d_out) {
+  const size_t l = (size_t)1 << log_l;
+  hipLaunchKernelGGL(kzg_cells_combine, dim3((unsigned)((l + 255) / 256)), dim3(256), 0, ctx->stream, d_c, d_w, d_rho, m, log_l, d_out);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+
 }  // namespace bp

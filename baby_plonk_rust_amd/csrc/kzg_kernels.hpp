@@ -131,4 +131,25 @@ __global__ void __launch_bounds__(256) kzg_lincomb(KzgCols a, size_t n, fr_t* __
   store_fr(&g[i], kzg_combine_at(a, i));
 }
 
+// ---- cell claims (bp_kzg_verify_cells_reduce): out[t] = - sum_{i<m} rho_i w_i^t c[i l + t], t < l = 2^log_l ---------------------------
+// c: the m rows after their inverse transform of length l (l^-1 included), so that w_i^t c[i l + t] with w_i = omega^(-k_i) is
+// coefficient t of the interpolant of claim i on its coset; out: the scalars of P_0 .. P_{l-1} in B.  One lane per t walks the m
+// claims (t < 2^24 is one exponent limb): m x ~50 products per lane, l lanes.  Reads c below m l, w and rho below m; writes out below l.
+__global__ void __launch_bounds__(256) kzg_cells_combine(const fr_t* __restrict__ c, const fr_t* __restrict__ w, const fr_t* __restrict__ rho, size_t m,
+                                                          uint32_t log_l, fr_t* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ((size_t)1 << log_l)) return;
+  const uint32_t e[1] = {(uint32_t)t};
+  fr_t acc = Fr::zero();
+  for (size_t i = 0; i < m; i++) {
+    fr_t p, v = load_fr(&c[(i << log_l) + t]);
+    Fr::pow(p, load_fr(&w[i]), e, 1);
+    Fr::mul(p, p, load_fr(&rho[i]));
+    Fr::mul(p, p, v);
+    Fr::add(acc, acc, p);
+  }
+  Fr::neg(acc, acc);
+  store_fr(&out[t], acc);
+}
+
 }  // namespace bp

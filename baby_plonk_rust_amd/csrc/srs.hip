@@ -260,4 +260,102 @@ int open_all_chat_run(bp_ctx* ctx, uint32_t log_n, const fr_t* d_f, size_t n_val
   return BP_OK;
 }
 
+// ---- the n / l cell proofs of a polynomial (kzg_open_cosets.hpp); log_l = 0 is open_all itself ---------------------------------------
+// the two projective buffers at `points` points each, and the twiddles of the lengths R = 2r and r (open_all's, for log_r)
+static int open_cosets_bufs(bp_ctx* ctx, uint32_t log_r, size_t points, OpenAllBufs* o) {
+  BP_TRY(ws_get(ctx, "srs.g1_ntt_a", points * sizeof(g1_proj), (void**)&o->a));
+  BP_TRY(ws_get(ctx, "srs.g1_ntt_b", points * sizeof(g1_proj), (void**)&o->b));
+  return open_all_bufs(ctx, log_r, o);                   // grow-only workspaces: the same two buffers, not smaller
+}
+int open_cosets_twiddles_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l) {
+  OpenAllBufs w;
+  return open_cosets_bufs(ctx, log_n - log_l, (size_t)1 << log_n, &w);      // what open_cosets_proofs_run asks for
+}
+// ev[k] -> ev[k + 1]: launch k of a sequence
+static inline int pass_mark(bp_ctx* ctx, hipEvent_t* ev, uint32_t* k) {
+  BP_HIP(ctx, hipGetLastError());
+  BP_HIP(ctx, hipEventRecord(ev[++*k], ctx->stream));
+  return BP_OK;
+}
+// d_table[j R + i] = DFT_R(S^(j))_i, j < l, i < R = 2n / l, of the first n - l points of d_srs: affine.  Waits for the stream; appends
+// its log_R pass times.  log_l < log_n < G1_NTT_MAX_LOG.
+int open_cosets_table_run(bp_ctx* ctx, const g1_affine* d_srs, uint32_t log_n, uint32_t log_l, g1_affine* d_table) {
+  if (log_l == 0) return open_all_table_run(ctx, d_srs, log_n, d_table);
+  const size_t n = (size_t)1 << log_n;
+  const uint32_t log_R = log_n - log_l + 1;
+  OpenAllBufs w;
+  BP_TRY(open_cosets_bufs(ctx, log_n - log_l, 2 * n, &w));
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "kzg.oc_table", log_R + 1, hipEventDefault, &ev));
+  g1_proj *cur = w.a, *oth = w.b;
+  const dim3 grid((unsigned)((n + 255) / 256));          // l transforms of R / 2 butterflies: n lanes in every pass
+  uint32_t k = 0;
+  BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+  hipLaunchKernelGGL(g1_ntt_cosets_table_pass0, grid, dim3(256), 0, ctx->stream, log_n, log_l, d_srs, cur);
+  BP_TRY(pass_mark(ctx, ev, &k));
+  for (uint32_t s = 1; s < log_R; s++) {
+    hipLaunchKernelGGL(g1_ntt_batch_pass, grid, dim3(256), 0, ctx->stream, log_R, log_l, s, (const g1_proj*)cur, oth, (const fr_t*)w.tw_big);
+    BP_TRY(pass_mark(ctx, ev, &k));
+    std::swap(cur, oth);
+  }
+  BP_TRY(srs_from_projective_run(ctx, cur, 2 * n, d_table));
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  return open_all_pass_times(ctx, ev, log_R);
+}
+// d_out[k] = the proof of cell k < r, affine, from the table and d_sc[j R + i] = R^-1 DFT_R(c^(j))_i (Montgomery): the multiplication,
+// the log_l - 1 halving passes, the inverse transform of length R, the final transform of length r, the normalisation.  `mid` is
+// recorded in front of the final transform.  Waits for the stream; appends the log_l + log_R + log_r pass times in that order.
+int open_cosets_proofs_run(bp_ctx* ctx, const g1_affine* d_table, const fr_t* d_sc, uint32_t log_n, uint32_t log_l, g1_affine* d_out, hipEvent_t mid) {
+  if (log_l == 0) return open_all_proofs_run(ctx, d_table, d_sc, log_n, d_out, mid);
+  const size_t n = (size_t)1 << log_n;
+  const uint32_t log_r = log_n - log_l, log_R = log_r + 1, passes = log_l + log_R + log_r;
+  const size_t r = (size_t)1 << log_r;
+  OpenAllBufs w;
+  BP_TRY(open_cosets_bufs(ctx, log_r, n, &w));           // n >= R: row 0 of the products, then both buffers of the transforms
+  hipEvent_t* ev;
+  BP_TRY(ev_get(ctx, "kzg.oc_proofs", passes + 1, hipEventDefault, &ev));
+  g1_proj *cur = w.a, *oth = w.b;
+  uint32_t k = 0;
+  BP_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+  hipLaunchKernelGGL(g1_ntt_cosets_mul_pass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, log_n, log_l, d_table, d_sc, cur);
+  BP_TRY(pass_mark(ctx, ev, &k));
+  for (size_t half = n >> 1; half >= 2 * r; half >>= 1) {
+    hipLaunchKernelGGL(g1_ntt_cosets_halve_pass, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, ctx->stream, (uint64_t)half, cur);
+    BP_TRY(pass_mark(ctx, ev, &k));
+  }
+  for (uint32_t s = 0; s < log_R; s++) {
+    hipLaunchKernelGGL(g1_ntt_pass<false>, dim3((unsigned)((r + 255) / 256)), dim3(256), 0, ctx->stream, log_R, s, (const g1_affine*)nullptr,
+                       (const g1_proj*)cur, oth, (const fr_t*)w.tw_big, Fr::zero());
+    BP_TRY(pass_mark(ctx, ev, &k));
+    std::swap(cur, oth);
+  }
+  BP_HIP(ctx, hipEventRecord(mid, ctx->stream));
+  hipLaunchKernelGGL(g1_ntt_final_pass0, dim3((unsigned)((r / 2 + 255) / 256)), dim3(256), 0, ctx->stream, log_r, (const g1_proj*)cur, oth);
+  BP_TRY(pass_mark(ctx, ev, &k));
+  std::swap(cur, oth);                                   // cur: what pass 0 wrote; oth: h, free from pass 1 on
+  for (uint32_t s = 1; s < log_r; s++) {
+    hipLaunchKernelGGL(g1_ntt_pass<false>, dim3((unsigned)((r / 2 + 255) / 256)), dim3(256), 0, ctx->stream, log_r, s, (const g1_affine*)nullptr,
+                       (const g1_proj*)cur, oth, (const fr_t*)w.tw_small, Fr::zero());
+    BP_TRY(pass_mark(ctx, ev, &k));
+    std::swap(cur, oth);
+  }
+  BP_TRY(srs_from_projective_run(ctx, cur, r, d_out));
+  BP_HIP(ctx, stream_wait(ctx->stream));
+  return open_all_pass_times(ctx, ev, passes);
+}
+// d_out[j R + t] = scale c^(j)_t, j < l, t < R (srs_kernels.hpp: open_cosets_chat_fill)
+int open_cosets_chat_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const fr_t* d_f, size_t n_values, const fr_t& scale, fr_t* d_out) {
+  const size_t N = (size_t)2 << log_n;
+  hipLaunchKernelGGL(open_cosets_chat_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, log_n, log_l, d_f, n_values, scale, d_out);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+// d_out[k l + j] = d_in[k + r j]: the n values in cell order; d_out must not be d_in
+int open_cosets_cell_order_run(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const fr_t* d_in, fr_t* d_out) {
+  const size_t n = (size_t)1 << log_n;
+  hipLaunchKernelGGL(open_cosets_cell_order, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, log_n, log_l, d_in, d_out);
+  BP_HIP(ctx, hipGetLastError());
+  return BP_OK;
+}
+
 }  // namespace bp

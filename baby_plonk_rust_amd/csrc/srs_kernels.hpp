@@ -8,6 +8,9 @@
 //   srs_scale      : out_i = k_i P_i, one variable-base multiplication per lane (a ceremony contribution, bp_srs_scale)
 //   g1_ntt_pass    : one pass of the inverse transform over G1 (bp_srs_lagrange); g1_ntt_table_pass0 / _toeplitz_pass0 / _final_pass0 and
 //                    open_all_chat_fill: pass 0 of the three transforms behind bp_kzg_open_all and its scalar layout (kzg_open_all.hpp)
+//   g1_ntt_cosets_* : the cell proofs of bp_kzg_open_cosets (kzg_open_cosets.hpp): the l side-by-side table transforms
+//                    (g1_ntt_cosets_table_pass0, g1_ntt_batch_pass), the two-products-per-lane multiplication and the halving
+//                    additions (g1_ntt_cosets_mul_pass, g1_ntt_cosets_halve_pass), the scalar and value layouts
 #pragma once
 #include "g1.hpp"
 #include "g1_28.hpp"
@@ -15,6 +18,7 @@
 #include "g1_mul_split28.hpp"
 #include "g1_ntt.hpp"
 #include "kzg_open_all.hpp"
+#include "kzg_open_cosets.hpp"
 
 namespace bp {
 
@@ -356,6 +360,53 @@ __global__ void __launch_bounds__(256) open_all_chat_fill(uint32_t log_n, const 
   fr_t v = Fr::zero();
   if (k != OPEN_ALL_NONE && k < n_values) Fr::mul(v, f[k], scale);
   out[t] = v;
+}
+
+// ---- the n / l cell proofs of a polynomial (kzg_open_cosets.hpp) ---------------------------------------------------------------------
+// One lane per butterfly or per output point.  Bounds: the table pass reads srs[k] only for k <= n - l - 1 (open_cosets_shat) and
+// writes the 2n slots of the l transforms; the batch pass reads and writes inside its own sub-transform; the multiplication reads
+// table and sc below 2n and writes dst below n; the halving pass touches buf below 2 half.
+__global__ void __launch_bounds__(256) g1_ntt_cosets_table_pass0(uint32_t log_n, uint32_t log_l, const g1_affine* __restrict__ srs,
+                                                                   g1_proj* __restrict__ dst) {
+  const uint64_t B = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (B >= ((uint64_t)1 << log_n)) return;                           // l transforms of R / 2 = r butterflies
+  open_cosets_table_pass0_at(log_n, log_l, B, srs, dst);
+}
+// pass s >= 1 of 2^log_count transforms of 2^log_len points side by side: the sub-transform is the high bits of the butterfly id
+__global__ void __launch_bounds__(256) g1_ntt_batch_pass(uint32_t log_len, uint32_t log_count, uint32_t s, const g1_proj* __restrict__ src,
+                                                           g1_proj* __restrict__ dst, const fr_t* __restrict__ tw) {
+  const uint64_t B = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (B >= ((uint64_t)1 << (log_len - 1 + log_count))) return;
+  open_cosets_batch_pass_at(log_len, s, B, src, dst, tw);
+}
+// two scalar multiplications per lane, each with a scalar of its own (the divergence of g1_ntt_toeplitz_pass0), and one addition
+__global__ void __launch_bounds__(256) g1_ntt_cosets_mul_pass(uint32_t log_n, uint32_t log_l, const g1_affine* __restrict__ table,
+                                                                const fr_t* __restrict__ sc, g1_proj* __restrict__ dst) {
+  const uint64_t B = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (B >= ((uint64_t)1 << log_n)) return;
+  open_cosets_mul_at(log_n, log_l, B, table, sc, dst);
+}
+__global__ void __launch_bounds__(256) g1_ntt_cosets_halve_pass(uint64_t half, g1_proj* buf) {
+  const uint64_t B = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (B >= half) return;
+  open_cosets_halve_at(half, B, buf);
+}
+// out[j R + t] = scale * c^(j)_t (Montgomery): the l columns of the batched Fr transform, from f[0 .. n_values), the rest zero
+__global__ void __launch_bounds__(256) open_cosets_chat_fill(uint32_t log_n, uint32_t log_l, const fr_t* __restrict__ f, size_t n_values, fr_t scale,
+                                                               fr_t* __restrict__ out) {
+  const uint64_t at = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (at >= ((uint64_t)2 << log_n)) return;
+  const uint32_t log_R = log_n - log_l + 1;
+  const uint64_t k = open_cosets_chat(log_n, log_l, at >> log_R, at & (((uint64_t)1 << log_R) - 1));
+  fr_t v = Fr::zero();
+  if (k != OPEN_ALL_NONE && k < n_values) Fr::mul(v, f[k], scale);
+  out[at] = v;
+}
+// out[k l + j] = in[k + r j]: the n values f(omega^i) in cell order
+__global__ void __launch_bounds__(256) open_cosets_cell_order(uint32_t log_n, uint32_t log_l, const fr_t* __restrict__ in, fr_t* __restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ((uint64_t)1 << log_n)) return;
+  out[c] = in[open_cosets_value_source(log_n, log_l, c)];
 }
 
 }  // namespace bp

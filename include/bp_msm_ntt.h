@@ -648,6 +648,41 @@ int  bp_kzg_open_all_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_poly
  * Toeplitz transform, final transform + normalisation + encoding. */
 int  bp_kzg_open_all_last_stats(bp_ctx* ctx, float stage_ms[4]);
 
+/* ---- cell proofs: the n / l coset multi-proofs of ONE polynomial in one call, and the reduction of m cell claims ----
+ * n = 2^log_n, l = 2^log_l <= n, r = n / l, w = root_of_unity(n).  Cell k < r is the coset { w^(k + r j) : j < l }; its values are
+ * v_{k,j} = f(w^(k + r j)) and its ONE proof is pi_k = [q_k(tau)] G with q_k = f div (x^l - a_k), a_k = w^(k l): the second half of
+ * Feist, Khovratovich, and the shape of a data-availability cell.  l Toeplitz products of length r are summed (a table of l
+ * transforms of 2r points side by side, ONE batched Fr transform, two scalar multiplications per GPU lane and log_l - 1 passes of
+ * additions), one inverse transform of 2r points and one DFT of r points over G1 follow.  log_l = 0 is bp_kzg_open_all, byte for byte.
+ *   srs_handle, poly, basis, scalar_fmt: as for bp_kzg_open_all.  Only the first n - l points are used; n - l > srs_len is BP_ERR_LENGTH.
+ *   log_n, log_l   log_l > log_n is BP_ERR_INVALID_ARG, log_n >= 24 BP_ERR_TOO_LARGE.  log_l == log_n: one proof, the identity (the
+ *                  quotient is zero); the values are written and no kernel over G1 runs.
+ *   values         n scalars in CELL ORDER, values[k l + j] = f(w^(k + r j)), or NULL.   proofs96: r x 96 bytes, proof k of cell k.
+ * A rejected call writes nothing.  Stage times: bp_kzg_open_all_last_stats (table | field work | multiplication, halving and inverse
+ * transform | final transform, normalisation, encoding).  A bp_init_multi context collects the points on its primary device.
+ *
+ * bp_srs_open_cosets_prepare builds and keeps the table for (log_n, log_l): 2n x 96 bytes, in the SRS's ONE table slot.  The slot's
+ * key is (log_n, log_l) and bp_srs_open_all_prepare / bp_kzg_open_all use log_l = 0: a call with another key replaces the table. */
+int  bp_srs_open_cosets_prepare(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n, uint32_t log_l);
+int  bp_kzg_open_cosets(bp_ctx* ctx, uint64_t srs_handle, const void* poly, size_t n_values, int basis, int scalar_fmt,
+                        uint32_t log_n, uint32_t log_l, void* values, uint8_t* proofs96);
+int  bp_kzg_open_cosets_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_poly, size_t n_values, int basis,
+                               uint32_t log_n, uint32_t log_l, void* values_mont_host, uint8_t* proofs96);
+/* m cell claims (C_i, k_i, v_{i,0} .. v_{i,l-1}, pi_i) reduced to out192 = A || B, the record of bp_pairing_check:
+ *   A = sum_i rho_i pi_i          B = sum_i rho_i (C_i + a_{k_i} pi_i) - sum_{t<l} (sum_i rho_i c_{i,t}) P_t
+ * with c_{i,t} = w^(-k_i t) l^-1 sum_j v_{i,j} zeta^(-j t), zeta = w^r: the coefficients of the interpolant of the values on the coset.
+ * The batch holds iff pairing(A, [tau^l]_2) == pairing(B, G2Affine::generator()): bp_pairing_check with [tau^l]_2 passed where x_2
+ * goes.  That G2 point is the CALLER'S (ceremonies ship the G2 powers); this call does not decide the pairing.
+ *   srs_handle   a powers-of-tau SRS with at least l points (BP_ERR_BASIS, BP_ERR_LENGTH).  log_l > log_n: BP_ERR_INVALID_ARG; log_n >= 24: BP_ERR_TOO_LARGE.
+ *   cell_index   m indices; one >= r is BP_ERR_INVALID_ARG with the claim in *first_bad.
+ *   values       m x l scalars in scalar_fmt, row i = claim i in the cell order of bp_kzg_open_cosets; a canonical-bytes value >= q
+ *                (or weight) is BP_ERR_BAD_SCALAR with the claim in *first_bad.
+ *   weights, checks, first_bad, m == 0: as for bp_kzg_verify_reduce.
+ * One batched inverse Fr transform of the m rows, one kernel for the weights and sums, two MSMs (over 2m + l and m points).  Blocking. */
+int  bp_kzg_verify_cells_reduce(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n, uint32_t log_l, const uint8_t* commitments96,
+                                const uint32_t* cell_index, const void* values, const uint8_t* proofs96, size_t m,
+                                const void* weights_or_null, int scalar_fmt, uint32_t checks, uint8_t out192[192], size_t* first_bad);
+
 /* ---- the structure of an SRS: powers of one tau, Lagrange points that belong to them, a ceremony contribution ----
  * bp_srs_load* and bp_srs_check_subgroup say that every point is a point of G1; nothing there says that the points are
  * G, tau G, tau^2 G, ... for ONE tau, or that x_2 is that tau in G2.  The calls below do, without knowing tau.

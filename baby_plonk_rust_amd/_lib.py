@@ -49,6 +49,7 @@ SRS_CHECK_SUBGROUP = 1          # BP_SRS_CHECK_SUBGROUP (bp_srs_load_compressed4
 SRS_CHECK_GENERATOR = 2         # BP_SRS_CHECK_GENERATOR (bp_srs_check_powers checks)
 COMM_ID_BYTES = 128             # BP_COMM_ID_BYTES (RCCL's ncclUniqueId)
 BASIS_LAGRANGE, BASIS_MONOMIAL = 0, 1
+KZG_RECOVER_WALK = 256          # csrc/kzg_recover.hpp: roots per slice of the vanishing evaluations of bp_kzg_recover
 
 _vp, _sz, _u64, _u32, _int, _cp = C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p
 _pp = C.POINTER
@@ -124,6 +125,10 @@ SIGNATURES = {
     "bp_kzg_open_cosets": (_int, [_vp, _u64, _vp, _sz, _int, _int, _u32, _u32, _vp, _vp]),
     "bp_kzg_open_cosets_device": (_int, [_vp, _u64, _vp, _sz, _int, _u32, _u32, _vp, _vp]),
     "bp_kzg_verify_cells_reduce": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _int, _u32, _vp, _vp]),
+    "bp_kzg_recover": (_int, [_vp, _u32, _u32, _vp, _vp, _sz, _sz, _int, _vp, _pp(_sz)]),
+    "bp_kzg_recover_device": (_int, [_vp, _u32, _u32, _vp, _vp, _sz, _sz, _vp, _pp(_sz)]),
+    "bp_kzg_recover_cells": (_int, [_vp, _u64, _u32, _u32, _vp, _vp, _sz, _sz, _int, _vp, _vp, _pp(_sz)]),
+    "bp_kzg_recover_last_stats": (_int, [_vp, _vp]),
     "bp_msm_g1": (_int, [_vp, _u64, _vp, _sz, _int, _vp]),
     "bp_msm_g1_projective144": (_int, [_vp, _vp, _sz, _vp, _sz, _int, _vp]),
     "bp_msm_g1_partial": (_int, [_vp, _u64, _sz, _vp, _sz, _int, _int, _vp]),

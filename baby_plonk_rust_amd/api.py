@@ -520,6 +520,13 @@ class Context:
         self.check(self._lib.bp_kzg_open_all_last_stats(self._h, ms), "bp_kzg_open_all_last_stats")
         return dict(zip(("table_ms", "field_ms", "toeplitz_ms", "final_ms"), [float(v) for v in ms]))
 
+    def kzg_recover_stats(self):
+        """milliseconds of the four stages of the last accepted recover_polynomial(_device) / Setup.recover_cells on this context;
+        vanishing_ms and coset_ms are 0 when no cell was missing"""
+        ms = (C.c_float * 4)()
+        self.check(self._lib.bp_kzg_recover_last_stats(self._h, ms), "bp_kzg_recover_last_stats")
+        return dict(zip(("vanishing_ms", "spread_ms", "coset_ms", "check_ms"), [float(v) for v in ms]))
+
     # ---- the structure of an SRS (capi_srs_check.hip) ----
     def srs_powers_reduce(self, handle, rho, first=0, n_pairs=None):
         """bp_srs_powers_reduce: (A96, B96) = (sum_i rho^i P_{first+i}, sum_i rho^i P_{first+i+1}) over n_pairs pairs (default: all
@@ -934,6 +941,65 @@ class DevicePolynomial(_PolynomialOps):
         return DevicePolynomial(self.t[lo:hi].contiguous(), self.basis, self.ctx)
 
 
+def _recover_args(name, indices, cell_size, group_order, n_coeffs):
+    """(log_n, log_l, the indices as uint32, n_coeffs) of a recovery; n_coeffs=None is group_order // 2"""
+    log_n, log_l = Setup._cell_logs(name, group_order, cell_size)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    if ((idx < 0) | (idx >= 1 << 32)).any():
+        raise BpError(-1, name, "a cell index outside 0 .. 2^32")
+    return log_n, log_l, idx.astype(np.uint32), max(group_order // 2, 1) if n_coeffs is None else int(n_coeffs)
+
+
+def _recover_check(ctx, rc, bad, name):
+    """raise for rc != 0 with `index` = first_bad: the position in `indices` (a bad or repeated index, a value >= q) or, for
+    BP_ERR_ASSERT, the lowest non-zero coefficient index of the interpolant"""
+    try:
+        ctx.check(rc, name)
+    except BpError as e:
+        e.index = bad.value if bad.value != _SIZE_MAX else None
+        raise
+
+
+def recover_polynomial(indices, cells, group_order, n_coeffs=None, ctx=None, fmt=FR_MONT):
+    """the polynomial of fewer than n_coeffs coefficients that takes the given cells (bp_kzg_recover): a Monomial Polynomial of n_coeffs
+    coefficients.  indices: m distinct cell indices in any order; cells: [m, l, 4] uint64 Montgomery limbs (fmt=FR_MONT) or
+    [m, l, 32] uint8 canonical little-endian bytes (FR_BYTES_LE), cells[i] being cell indices[i] of the domain of group_order points in
+    the cell order of Setup.open_cosets.  n_coeffs=None means group_order // 2, the rate-1/2 extension of a data-availability column.
+    Needs m * l >= n_coeffs.  With m * l > n_coeffs the cells are checked against each other: BpError BP_ERR_ASSERT (index = the
+    lowest non-zero coefficient of their interpolant) if no such polynomial exists.  With m * l == n_coeffs there is NOTHING to check:
+    the interpolant of whatever was given comes back.  Other errors carry the position in `indices` in `index`."""
+    c = ctx or default_context()
+    width, dt = (4, np.uint64) if fmt == FR_MONT else (32, np.uint8)
+    v = np.ascontiguousarray(cells, dtype=dt)
+    if v.ndim != 3 or v.shape[2] != width or v.shape[0] != len(indices):
+        raise BpError(-6, "recover_polynomial", "cells: [m, l, %d] expected" % width)
+    log_n, log_l, idx, d = _recover_args("recover_polynomial", indices, v.shape[1], group_order, n_coeffs)
+    out, bad = np.zeros((min(max(d, 1), group_order), 4), dtype=np.uint64), C.c_size_t(-1)      # d > group_order is refused before a write
+    rc = c._lib.bp_kzg_recover(c._h, log_n, log_l, idx.ctypes.data, v.ctypes.data, len(idx), d, fmt, out.ctypes.data, C.byref(bad))
+    _recover_check(c, rc, bad, "recover_polynomial")
+    if fmt != FR_MONT:
+        out = scalars_from_ints([int.from_bytes(out[i].tobytes(), "little") for i in range(d)])
+    return Polynomial(out[:d], BASIS_MONOMIAL, c)
+
+
+def recover_polynomial_device(indices, d_cells, cell_size, group_order, n_coeffs=None, ctx=None):
+    """recover_polynomial with the cells in HBM (bp_kzg_recover_device): d_cells is a torch int64 tensor of m * cell_size Montgomery
+    scalars ([m, l, 4] or [m * l, 4]) on the context's device.  Returns a Monomial DevicePolynomial of n_coeffs coefficients, a view of a
+    buffer of group_order scalars whose other places are zero (`.t._base` keeps it alive)."""
+    import torch
+    c = ctx or default_context()
+    log_n, log_l, idx, d = _recover_args("recover_polynomial_device", indices, cell_size, group_order, n_coeffs)
+    t = d_cells.contiguous()
+    if t.dtype != torch.int64 or t.numel() != len(idx) * cell_size * 4:
+        raise BpError(-6, "recover_polynomial_device", "d_cells: %d x %d Montgomery scalars (int64 limbs) expected" % (len(idx), cell_size))
+    out = torch.empty((group_order, 4), dtype=torch.int64, device=torch.device("cuda", c.device))
+    torch.cuda.current_stream().synchronize()
+    bad = C.c_size_t(-1)
+    rc = c._lib.bp_kzg_recover_device(c._h, log_n, log_l, idx.ctypes.data, t.data_ptr(), len(idx), d, out.data_ptr(), C.byref(bad))
+    _recover_check(c, rc, bad, "recover_polynomial_device")
+    return DevicePolynomial(out[:d], BASIS_MONOMIAL, c)
+
+
 def commit_device(setup, poly):
     """Setup::commit (setup.rs:32-37) of an HBM-resident polynomial"""
     c = setup.ctx
@@ -1215,6 +1281,24 @@ class Setup:
         fn = getattr(c._lib, "bp_kzg_open_cosets" + poly._SUFFIX)
         c.check(fn(*head, *poly._FMT, log_n, log_l, cells.ctypes.data, proofs.ctypes.data), "Setup.open_cosets")
         return cells, proofs
+
+    def recover_cells(self, indices, cells, group_order, n_coeffs=None):
+        """ALL group_order / cell_size cells and cell proofs of a column from m of its cells (bp_kzg_recover_cells: recover_polynomial,
+        then open_cosets on the coefficients where they lie, in HBM): returns (cells [r, l, 4] uint64, proofs [r, 96] uint8), the
+        shapes of open_cosets, the given cells among them as they were given.  indices, cells ([m, l, 4] Montgomery limbs), n_coeffs
+        (None: group_order // 2) and the errors are recover_polynomial's; the Setup is open_cosets' (the first n - l powers of tau)."""
+        c = self.ctx
+        v = np.ascontiguousarray(cells, dtype=np.uint64)
+        if v.ndim != 3 or v.shape[2] != 4 or v.shape[0] != len(indices):
+            raise BpError(-6, "Setup.recover_cells", "cells: [m, l, 4] expected")
+        l = v.shape[1]
+        log_n, log_l, idx, d = _recover_args("Setup.recover_cells", indices, l, group_order, n_coeffs)
+        r = max(group_order // l, 1)
+        out, proofs, bad = np.zeros((r, l, 4), dtype=np.uint64), np.zeros((r, 96), dtype=np.uint8), C.c_size_t(-1)
+        rc = c._lib.bp_kzg_recover_cells(c._h, self.handle, log_n, log_l, idx.ctypes.data, v.ctypes.data, len(idx), d, FR_MONT, out.ctypes.data,
+                                         proofs.ctypes.data, C.byref(bad))
+        _recover_check(c, rc, bad, "Setup.recover_cells")
+        return out, proofs
 
     def cell_pairing_inputs(self, claims, group_order, weights=None, checks=0):
         """the claims of a list of CellOpening records (one cell size for all) reduced to (A96, B96): they hold iff

@@ -61,5 +61,14 @@ struct SrsShard {
 // is lifted to ctx.  srs_shards_checked refuses a range that does not lie inside the SRS instead of cutting it.
 int srs_shards(bp_ctx* ctx, uint64_t srs_handle, std::vector<SrsShard>* out, size_t first = 0, size_t n = SIZE_MAX);
 int srs_shards_checked(bp_ctx* ctx, uint64_t srs_handle, size_t first, size_t n, std::vector<SrsShard>* out);
+// capi_kzg_open_all.hip
+// the SRS and shape rules of bp_kzg_open_cosets; on BP_OK *e is the SRS's entry (the leader's, for a group)
+int open_cosets_srs_check(bp_ctx* ctx, uint64_t srs, uint32_t log_n, uint32_t log_l, bp::SrsEntry** e);
+// The cells and cell proofs of n_values <= n Montgomery coefficients resident on the context's device, behind open_cosets_srs_check:
+// what bp_kzg_open_cosets_device computes, with the results left in workspaces of the context.  *d_values_out (want_values): the n
+// values in cell order; *d_bytes_out: the n / l x 96 proof bytes, or nullptr where the one proof is the identity (log_l == log_n).
+// The stream has been waited for when *d_bytes_out is set, else the work is enqueued.
+int open_cosets_resident(bp_ctx* ctx, uint64_t srs, bp::SrsEntry* e, const bp::fr_t* d_poly, size_t n_values, uint32_t log_n, uint32_t log_l,
+                         bool want_values, bp::fr_t** d_values_out, uint8_t** d_bytes_out);
 // does an MSM of n points against this entry go through its fixed-base tables?
 bool srs_tables_pay(const bp::SrsEntry& e, size_t n);

@@ -221,7 +221,7 @@ int bp_kzg_open_all(bp_ctx* ctx, uint64_t srs_handle, const void* poly, size_t n
 }
 
 // ---- cell proofs: l = 2^log_l values and ONE proof per coset (kzg_open_cosets.hpp) -----------------------------------------------------
-static int open_cosets_srs_check(bp_ctx* ctx, uint64_t srs, uint32_t log_n, uint32_t log_l, SrsEntry** e) {
+int open_cosets_srs_check(bp_ctx* ctx, uint64_t srs, uint32_t log_n, uint32_t log_l, SrsEntry** e) {
   BP_TRY(srs_find(ctx, srs, e));
   if ((*e)->basis != BP_BASIS_MONOMIAL) return BP_FAIL(ctx, BP_ERR_BASIS, "kzg open cosets: the SRS must be powers of tau, not a Lagrange SRS");
   if (log_l > log_n) return BP_FAIL(ctx, BP_ERR_INVALID_ARG, "kzg open cosets: log_l > log_n (a cell larger than the domain)");
@@ -254,9 +254,17 @@ static int open_cosets_whole(bp_ctx* ctx, const fr_t* d_poly, size_t n_values, i
   BP_TRY(ws_get(ctx, "kzg.oa_values", n * sizeof(fr_t), (void**)&d_vals));
   BP_HIP(ctx, hipMemsetAsync(d_vals, 0, n * sizeof(fr_t), ctx->stream));
   if (n_values) BP_HIP(ctx, hipMemcpyAsync(d_vals, d_poly, n_values * sizeof(fr_t), hipMemcpyDeviceToDevice, ctx->stream));
-  if (basis == BP_BASIS_MONOMIAL) BP_TRY(ntt_run(ctx, d_vals, log_n, 0, 1, n));
+  if (basis == BP_BASIS_MONOMIAL && log_n) BP_TRY(ntt_run(ctx, d_vals, log_n, 0, 1, n));      // n = 1: the value is f_0
   *d_values_out = d_vals;
   return BP_OK;
+}
+
+// capi_common.hpp: the core behind the checks for coefficients that are in HBM already (bp_kzg_recover_cells hands its result over here)
+int open_cosets_resident(bp_ctx* ctx, uint64_t srs, SrsEntry* e, const fr_t* d_poly, size_t n_values, uint32_t log_n, uint32_t log_l, bool want_values,
+                         fr_t** d_values_out, uint8_t** d_bytes_out) {
+  *d_bytes_out = nullptr;
+  if (log_l == log_n) return open_cosets_whole(ctx, d_poly, n_values, BP_BASIS_MONOMIAL, log_n, want_values, d_values_out);
+  return open_all_core(ctx, srs, e, d_poly, n_values, BP_BASIS_MONOMIAL, log_n, log_l, want_values, d_values_out, d_bytes_out);
 }
 
 int bp_kzg_open_cosets_device(bp_ctx* ctx, uint64_t srs_handle, const void* d_poly, size_t n_values, int basis, uint32_t log_n, uint32_t log_l,

@@ -153,7 +153,9 @@ struct bp_ctx {
   float kzg_ms[3] = {0, 0, 0};
   // bp_kzg_open_all(_device): table build (0: it was there) | field work | Toeplitz transform | final transform, normalisation, encoding
   float kzg_open_all_ms[4] = {0, 0, 0, 0};
-  const void* open_all_tw_ptr = nullptr;             // the workspace "kzg.oa_tw" holds the twiddles of both lengths for this log_n
+  // bp_kzg_recover(_device, _cells): vanishing evaluations | spread + first inverse transform | coset division | check + output
+  float kzg_recover_ms[4] = {0, 0, 0, 0};
+  const void* open_all_tw_ptr = nullptr;            // the workspace "kzg.oa_tw" holds the twiddles of both lengths for this log_n
   uint32_t open_all_tw_log_n = 0;
   // bp_srs_check_powers / bp_srs_adopt_lagrange: reduces (adopt: comparisons of two MSMs) and host pairings of the last call and its
   // host wall time; bp_srs_scale: subgroup test | srs_scale | normalisation of the last call (HIP events; a group: the sum over its shards)

@@ -683,6 +683,47 @@ int  bp_kzg_verify_cells_reduce(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n
                                 const uint32_t* cell_index, const void* values, const uint8_t* proofs96, size_t m,
                                 const void* weights_or_null, int scalar_fmt, uint32_t checks, uint8_t out192[192], size_t* first_bad);
 
+/* ---- cell recovery: ONE polynomial, all its r cells and all r proofs rebuilt from m of the cells ----
+ * The third operation of a data-availability scheme (PeerDAS: recover_cells_and_kzg_proofs).  n, l, r, w and the cells as above;
+ * w_r = w^l.  Given m distinct cell indices in any order, their m x l values (row i = the cell cell_index[i], in cell order) and a
+ * degree bound n_coeffs = d (deg f < d, 1 <= d <= m l), with M the r - m missing indices and Z(x) = prod_{k in M} (x^l - w_r^k):
+ * Z is evaluated on the domain and on the domain shifted by s = 7 directly, r values each (its coefficients are never formed);
+ * (f Z) on the domain is the given values times Z, zero on the missing cells; one inverse transform, then a forward transform on the
+ * shifted domain, the division by Z there and one more inverse transform give g, the interpolant of the given values (deg g < m l).
+ * Four Fr transforms of length n (one when nothing is missing) and 2 r |M| products; nothing over G1.
+ *   cell_index    host memory, m indices.  One >= r is BP_ERR_INVALID_ARG with its position in *first_bad; a repeated one
+ *                 BP_ERR_INVALID_ARG with the position of the second occurrence.  These come first, then:
+ *   n_coeffs      0, > n or > m l (too few cells) is BP_ERR_LENGTH.
+ *   log_n, log_l  log_l > log_n is BP_ERR_INVALID_ARG; log_n >= 24 or r > 2^16 is BP_ERR_TOO_LARGE (Z is evaluated directly: at most
+ *                 2^33 products under this limit).  In a shape that is refused a repeated index is not looked for.
+ *   values        a canonical-bytes value >= q is BP_ERR_BAD_SCALAR with the cell's position in *first_bad.
+ *   consistency   the cells agree with SOME polynomial of degree < d exactly when coefficients d .. n - 1 of g are zero; otherwise
+ *                 the call fails with BP_ERR_ASSERT and *first_bad = the lowest non-zero coefficient index (it does not say which cell
+ *                 is wrong).  With m l == d there is no redundancy and NOTHING to check: the call returns the interpolant of
+ *                 whatever it was given, and a wrong value goes unnoticed.
+ *   first_bad     may be NULL; SIZE_MAX when no position applies.
+ * bp_kzg_recover: values and coeffs_out (n_coeffs scalars) in host memory, in scalar_fmt.
+ * bp_kzg_recover_device: d_values (m l Montgomery elements) and d_coeffs (room for n Montgomery elements, apart from d_values) in HBM
+ * on the context's primary device; the work is done in d_coeffs: on BP_OK its first n_coeffs elements are the result and the rest zero,
+ * after BP_ERR_ASSERT it holds the n coefficients of the interpolant (unspecified for callers), after any other refusal it is untouched.
+ * bp_kzg_recover_cells: the recovery, then the core of bp_kzg_open_cosets_device on the coefficients where they lie (they never
+ * leave HBM): values_out (n scalars in scalar_fmt, cell order, or NULL) and proofs96 (r x 96 bytes) are ALL cells and proofs, the
+ * given ones included.  SRS requirements and errors are bp_kzg_open_cosets' (a powers-of-tau SRS, n - l <= srs_len), checked after
+ * the rules above and before anything is computed; the proof stages' times stay in bp_kzg_open_all_last_stats.
+ * A rejected call writes nothing to its host outputs.  Null context or pointers and a bad format are BP_ERR_INVALID_ARG.  A
+ * bp_init_multi context runs on its primary device.  Blocking; ordered on the context's stream.
+ * bp_kzg_recover_last_stats: HIP-event milliseconds of the last accepted recovery: vanishing evaluations | spread + first inverse
+ * transform | coset division (three transforms) | check + output.  Entries 0 and 2 are 0 when no cell was missing; all four are 0
+ * after a call that BP_ERR_ASSERT refused. */
+int  bp_kzg_recover(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const uint32_t* cell_index, const void* values, size_t m,
+                    size_t n_coeffs, int scalar_fmt, void* coeffs_out, size_t* first_bad);
+int  bp_kzg_recover_device(bp_ctx* ctx, uint32_t log_n, uint32_t log_l, const uint32_t* cell_index, const void* d_values, size_t m,
+                           size_t n_coeffs, void* d_coeffs, size_t* first_bad);
+int  bp_kzg_recover_cells(bp_ctx* ctx, uint64_t srs_handle, uint32_t log_n, uint32_t log_l, const uint32_t* cell_index,
+                          const void* values, size_t m, size_t n_coeffs, int scalar_fmt, void* values_out, uint8_t* proofs96,
+                          size_t* first_bad);
+int  bp_kzg_recover_last_stats(bp_ctx* ctx, float stage_ms[4]);
+
 /* ---- the structure of an SRS: powers of one tau, Lagrange points that belong to them, a ceremony contribution ----
  * bp_srs_load* and bp_srs_check_subgroup say that every point is a point of G1; nothing there says that the points are
  * G, tau G, tau^2 G, ... for ONE tau, or that x_2 is that tau in G2.  The calls below do, without knowing tau.
